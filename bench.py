@@ -1,7 +1,13 @@
 #!/usr/bin/env python
 """bench.py -- query-points/s of the TDNet hot path (forward + loss + backward + Adam) on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--batch B]
+    python bench.py --gpus N --steps K --warmup W [--batch B] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times EXACTLY K steps and prints the headline line.  `--full` adds everything else the
+benchmark measures or checks: the median of `--reps` repetitions, the per-kernel table and roofline of the dominant kernel
+class (extra untimed steps), the step with a loss read-back, the host's enqueue pace on an idle GPU, the bf16 accuracy cost
+against the reference's fixture and the CPU baseline.  `--dump-outputs DIR` writes what the last timed step returned (the
+loss and the model's updated weights and buffers for a train step, the predictions for an eval step) as DIR/<name>.npy.
 
 One process per GPU (torch.distributed / RCCL for N > 1).  Started under torch.distributed.run (RANK / WORLD_SIZE in
 the environment) it is one rank of the job; started from a bare shell with --gpus N > 1 it launches the N ranks itself
@@ -26,6 +32,24 @@ if ROOT not in sys.path:
 
 N_SURF, N_QUERY = 2048, 8192
 FLOP_PER_QUERY_FWD_BWD = 14.3e6  # 117 GFLOP fwd+bwd per 8192-query shape
+DUMP_BUDGET_BYTES = 60 << 20     # --dump-outputs: at most 64 MB in all, .npy headers included
+
+
+def dump_outputs(dirname, tensors):
+    """Writes {name: tensor} as dirname/<name>.npy, floating tensors as float32, all others as float64.  Over the budget,
+    every array keeps the same fraction of its rows (first axis; elements of a 1-D array), drawn with a fixed seed: the
+    same arguments give the same sample."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {k: (t.detach().float() if t.is_floating_point() else t.detach().double()).cpu().numpy()
+              for k, t in tensors.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    keep = min(1.0, DUMP_BUDGET_BYTES / total) if total else 1.0
+    for name, a in arrays.items():
+        if keep < 1.0 and a.ndim > 0:
+            n = max(1, int(a.shape[0] * keep))
+            a = a[np.sort(np.random.default_rng(0).permutation(a.shape[0])[:n])]
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def model_config():
@@ -194,6 +218,8 @@ def stub_main(args, rank, world):
         in_sync = bool(torch.equal(lo, hi))
     else:
         in_sync = True
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"loss": loss, **model.state_dict()})
     if rank == 0:
         total = world * args.batch * 64 * args.steps
         print(json.dumps({"metric": "stub rows/s (plumbing test, NOT a measurement)", "value": round(total / elapsed, 1),
@@ -238,10 +264,15 @@ def main():
     ap.add_argument("--batch", type=int, default=None,
                     help="shapes per GPU (weak scaling); default 32 for the train steps (BASELINE configs 3/4 per GPU), "
                          "8 for forward_eval (config 2), 4 for dense_inference (config 5)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--reps", type=int, default=3,
-                    help="timed repetitions of the K-step region (each bracketed by barrier + synchronize); the line reports "
-                         "the MEDIAN repetition as value / ms_per_step and min / max beside it")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: repetitions, per-kernel table and roofline, loss read-back, idle-GPU host pace, "
+                         "bf16 accuracy cost and CPU baseline (a plain run times its K steps once and reports only the headline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned as DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
+    ap.add_argument("--reps", type=int, default=None,
+                    help="with --full (default 3): timed repetitions of the K-step region (each bracketed by barrier + "
+                         "synchronize); the line reports the MEDIAN repetition as value / ms_per_step and min / max beside it")
     ap.add_argument("--workload", default="forward_train",
                     choices=["forward_train", "arbitrary_train", "forward_eval", "dense_inference"],
                     help="forward_train (default, the headline metric) | arbitrary_train (BASELINE config 3) | "
@@ -287,6 +318,9 @@ def main():
     args = ap.parse_args()
     if args.batch is None:
         args.batch = DEFAULT_BATCH[args.workload]
+    if args.reps is not None and not args.full:
+        ap.error("--reps needs --full (a plain run times its --steps steps once)")
+    reps_wanted = (3 if args.reps is None else args.reps) if args.full else 1
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args.gpus, sys.argv[1:]))
@@ -405,13 +439,15 @@ def main():
         return model(data["space_samples_src"], data["surface_samples_inputs"])
 
     def infer_step():
+        # (the predictions are returned beside their sum for --dump-outputs: a replay refills the tensors its capture returned)
         if pipe is not None:
             pipe.prefetch(data_next)
         with torch.no_grad():
-            out = forward().sum()
+            pred = forward()
+            out = pred.sum()
         if pipe is not None:
             pipe.rotate()
-        return out
+        return out, pred
 
     def step():
         # train_on_batch_with_cano (reference model/deformation_networks.py:63-77); the loss scalar is
@@ -539,7 +575,7 @@ def main():
     # spans the time the kernel waits for CUs held by the other stream.
     prof_iso = None
     dominant = "linear_bf16x3_kernel" if args.dtype == "f32" else "linear_bf16_kernel"
-    if not is_eval or graph is not None:      # (every rank runs it -- same program on every rank; rank 0 reports it)
+    if args.full and (not is_eval or graph is not None):      # (every rank runs it -- same program on every rank; rank 0 reports it)
         # (with graph replay this pass runs the EAGER step function: the kernels are the same, and a replay carries no events)
         from nsdp_amd import hip_linear
         one = eager_run if graph is not None else run
@@ -568,19 +604,21 @@ def main():
     # host pace with an EMPTY launch queue: one step enqueued right after a synchronize -- what the host needs for a step
     # when nothing pushes back (inside the timed region the enqueue calls also wait for queue / kernarg slots whenever the
     # GPU is the slower side, so `host_enqueue_ms_per_step` there converges to the step time itself)
-    t0 = time.perf_counter()
-    run()
-    host_unblocked = time.perf_counter() - t0
-    fence()
-    if os.environ.get("NSDP_BENCH_NO_EVENTS") != "1":    # (A/B knob: cost of the HIP events themselves)
-        profiling.start(only=[dominant] if dominant else None)
+    host_unblocked = None
+    if args.full:
+        t0 = time.perf_counter()
+        run()
+        host_unblocked = time.perf_counter() - t0
+        fence()
+        if os.environ.get("NSDP_BENCH_NO_EVENTS") != "1":    # (A/B knob: cost of the HIP events themselves)
+            profiling.start(only=[dominant] if dominant else None)
     comm_events.clear()
     reps = []
-    for _ in range(max(1, args.reps)):      # each repetition: EXACTLY K steps between fences, MAX over ranks
+    for _ in range(max(1, reps_wanted)):      # each repetition: EXACTLY K steps between fences, MAX over ranks
         fence()
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            loss = run()
+            out = run()
         t_enq = time.perf_counter() - t0       # host time to ENQUEUE the K steps (no sync inside a step)
         fence()
         el = time.perf_counter() - t0
@@ -592,7 +630,11 @@ def main():
     prof = profiling.stop()
     order = sorted(range(len(reps)), key=lambda i: reps[i][0])
     elapsed, t_enqueued = reps[order[len(order) // 2]]        # the median repetition is the reported one
+    loss, pred = out if is_eval else (out, None)
     final_loss = float(loss.item())
+    # what the last timed step returned, before any step of --full's extras runs
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"pred": pred} if is_eval else {"loss": loss, **model.state_dict()})
     comm_ms = None
     if comm_events:
         comm_ms = sum(a.elapsed_time(b) for a, b in comm_events) / len(comm_events)
@@ -600,7 +642,7 @@ def main():
     # model/deformation_networks.py:77) -- one host sync per step, behind which the next step's enqueue (3-5 ms of host time
     # for a replay, 20+ ms eager) is exposed.  Same K steps, same launcher, outside the contract's timed region.
     with_readback = None
-    if not is_eval:
+    if args.full and not is_eval:
         fence()
         t0 = time.perf_counter()
         for _ in range(args.steps):
@@ -615,7 +657,7 @@ def main():
     # of its launches inside the executor -- durations then include the time a kernel shares the chip with the other
     # stream's kernels, which the isolated pass above excludes on purpose.
     replayed = None
-    if graph is not None and dominant and hasattr(graph, "timed_replay"):
+    if args.full and graph is not None and dominant and hasattr(graph, "timed_replay"):
         try:
             fence()
             stem = dominant.replace("_kernels", "").replace("_kernel", "") + "_kernel"
@@ -630,7 +672,7 @@ def main():
     gc.enable()
     in_sync = dp.in_sync(model) if dp is not None else True
     parity = None
-    if rank == 0 and args.dtype == "bf16" and args.workload in ("forward_train", "arbitrary_train"):
+    if args.full and rank == 0 and args.dtype == "bf16" and args.workload in ("forward_train", "arbitrary_train"):
         parity = bf16_parity(args.workload, device)
 
     if rank == 0:
@@ -648,9 +690,6 @@ def main():
             "metric": names[0],
             "value": round(value, 1), "unit": "query-points/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": round(1e3 * elapsed / args.steps, 3),
-            "ms_per_step_reps": {"n": len(reps), "median": round(1e3 * elapsed / args.steps, 3),
-                                 "min": round(1e3 * reps[order[0]][0] / args.steps, 3),
-                                 "max": round(1e3 * reps[order[-1]][0] / args.steps, 3)},
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": args.dtype,
             "data": "synthetic",
             "config": {"workload": f"{names[1]}, "
@@ -663,15 +702,12 @@ def main():
                        "global_batch": world * args.batch, "n_surf": N_SURF, "n_query": n_query,
                        "parallelism": f"dp{world}"},
             "per_gpu": round(value / world, 1),
-            "ms_per_step_with_loss_readback": (round(1e3 * with_readback / args.steps, 3) if with_readback is not None else None),
             "host_enqueue_ms_per_step": round(1e3 * t_enqueued / args.steps, 3),
-            "host_enqueue_unblocked_ms": round(1e3 * host_unblocked, 3),
             "step_launch": graph_note,
             "geometry": ("pipelined: every step computes the next batch's index sets (FPS, kNN, inverse lists) beside its forward "
                          "pass and uses the ones the previous step computed for it" if pipe is not None else
                          "inline: searched inside the step's forward pass"),
             "cpu_mask": cpu_mask,
-            "parity_l2_vs_fp32": parity,
             "comm": {"backend": (dist.get_backend() if dist.is_initialized() else None),
                      "world_size": (dist.get_world_size() if dist.is_initialized() else 1),
                      "grad_bytes_per_step": (reducer.nbytes if reducer is not None else None),
@@ -684,15 +720,25 @@ def main():
             "ranks_in_sync": in_sync,
             "model_tflops": round(value * FLOP_PER_QUERY_FWD_BWD / 1e12, 2) if args.workload == "forward_train" else None,
             "final_loss": round(final_loss, 6),
-            "roofline": profiling.roofline(prof, prof_iso,
-                                           pmc_matches=(args.workload == "forward_train" and args.batch == 32),
-                                           pmc_suffix=("" if args.dtype == "f32" else "_bf16"), replayed=replayed),
-            "kernels": profiling.summary(prof_iso if prof_iso else prof),
-            "kernels_from": ("2 untimed steps, every launch timed, weight gradients on the main stream" if prof_iso
-                             else "timed region"),
         }
-        line["cpu_baseline"] = None if (args.no_cpu_baseline or world > 1 or args.workload != "forward_train") \
-            else cpu_baseline()
+        if args.full:
+            line.update({
+                "ms_per_step_reps": {"n": len(reps), "median": round(1e3 * elapsed / args.steps, 3),
+                                     "min": round(1e3 * reps[order[0]][0] / args.steps, 3),
+                                     "max": round(1e3 * reps[order[-1]][0] / args.steps, 3)},
+                "ms_per_step_with_loss_readback": (round(1e3 * with_readback / args.steps, 3)
+                                                   if with_readback is not None else None),
+                "host_enqueue_unblocked_ms": round(1e3 * host_unblocked, 3),
+                "parity_l2_vs_fp32": parity,
+                "roofline": profiling.roofline(prof, prof_iso,
+                                               pmc_matches=(args.workload == "forward_train" and args.batch == 32),
+                                               pmc_suffix=("" if args.dtype == "f32" else "_bf16"), replayed=replayed),
+                "kernels": profiling.summary(prof_iso if prof_iso else prof),
+                "kernels_from": ("2 untimed steps, every launch timed, weight gradients on the main stream" if prof_iso
+                                 else "timed region"),
+            })
+            line["cpu_baseline"] = None if (args.no_cpu_baseline or world > 1 or args.workload != "forward_train") \
+                else cpu_baseline()
         # RCCL writes its version banner through C stdio, which a pipe buffers until exit: flush it first, so that the
         # JSON line is the LAST line of stdout for whoever parses it
         try:

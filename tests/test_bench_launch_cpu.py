@@ -45,3 +45,18 @@ def test_single_rank_needs_no_launcher():
 def test_world_size_mismatch_is_an_error_not_an_assert():
     p, _ = _run(["--gpus", "2", "--stub-step"], env_extra={"WORLD_SIZE": "4", "RANK": "0"})
     assert p.returncode != 0 and "WORLD_SIZE" in p.stderr
+
+
+@pytest.mark.timeout(300)
+def test_dump_outputs_from_rank_0(tmp_path):
+    """--dump-outputs: rank 0 writes the last timed step's loss and the updated weights as float32 .npy files."""
+    import numpy as np
+    p, lines = _run(["--gpus", "2", "--backend", "gloo", "--stub-step", "--steps", "3", "--warmup", "1",
+                     "--dump-outputs", str(tmp_path)])
+    assert p.returncode == 0, p.stderr[-2000:]
+    line = json.loads(lines[0])
+    files = sorted(os.listdir(tmp_path))
+    assert files == ["decoder.bias.npy", "decoder.weight.npy", "encoder.bias.npy", "encoder.weight.npy", "loss.npy"]
+    arrays = {f: np.load(os.path.join(tmp_path, f)) for f in files}
+    assert all(a.dtype == np.float32 for a in arrays.values()) and arrays["encoder.weight.npy"].shape == (16, 16)
+    assert abs(float(arrays["loss.npy"]) - line["final_loss"]) <= 1e-6

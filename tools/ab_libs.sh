@@ -8,7 +8,7 @@ LIB=nsdp_amd/lib/libnsdp_hip.so
 cp $LIB /tmp/ab_A.so; cp "$B" /tmp/ab_B.so
 trap 'cp /tmp/ab_A.so $LIB' EXIT
 run() {
-  python bench.py --no-cpu-baseline --steps 20 --warmup 5 "${@:2}" 2>/dev/null | python -c "
+  python bench.py --full --no-cpu-baseline --steps 20 --warmup 5 "${@:2}" 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1]); r = d['roofline']
 print('$1', d['ms_per_step'], 'ms/step  frac', r['frac'], ' launch ms', r['avg_launch_ms'], ' frac_replayed', r.get('frac_replayed'))"

@@ -1,6 +1,6 @@
 """Forward and backward phase of a replayed train step from a rocprofv3 kernel trace: per phase the main queue's busy time and
 kernel-boundary gaps, and every kernel name by queue with count / total / average (in-step durations: beside the other stream).
-    rocprofv3 --kernel-trace --output-format csv -d DIR -o t -- python bench.py --reps 1 --steps 5 --warmup 2 --no-cpu-baseline
+    rocprofv3 --kernel-trace --output-format csv -d DIR -o t -- python bench.py --full --reps 1 --steps 5 --warmup 2 --no-cpu-baseline
     python tools/phase_breakdown.py DIR/**/t_kernel_trace.csv [rows per phase]"""
 import csv, sys, collections, re
 rows=[]

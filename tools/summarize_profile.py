@@ -1,7 +1,7 @@
 #!/usr/bin/env python
-"""Condenses rocprofv3 CSV output (gpurun_out/) into the small tracked summaries under profiles/.
+"""Condenses what tools/profile_round.sh wrote (rocprofv3 CSV output, bench lines) into the small tracked summaries under profiles/.
 
-    python tools/summarize_profile.py <round-tag>   # e.g. r1
+    python tools/summarize_profile.py <round-tag> [OUT]   # e.g. r1; OUT as given to profile_round.sh (default profile_out/)
 """
 import csv
 import collections
@@ -13,6 +13,7 @@ import sys
 tag = sys.argv[1] if len(sys.argv) > 1 else "r1"
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 out_dir = os.path.join(root, "profiles")
+src_dir = os.path.abspath(sys.argv[2]) if len(sys.argv) > 2 else os.path.join(root, "profile_out")
 os.makedirs(out_dir, exist_ok=True)
 
 
@@ -23,16 +24,16 @@ def short(name):
     return (m.group(1) if m else name)[:90]
 
 
-for suffix, title in (("", "python bench.py --eager --reps 1 --steps 5 --warmup 2 --no-cpu-baseline (the eager launcher: the same kernels as the graph replay, which the tracer does not need to see captured)"),
-                      ("_iso", "NSDP_WGRAD_STREAM=0 python bench.py --eager --reps 1 --steps 5 --warmup 2 --no-cpu-baseline "
+for suffix, title in (("", "python bench.py --full --eager --reps 1 --steps 5 --warmup 2 --no-cpu-baseline (the eager launcher: the same kernels as the graph replay, which the tracer does not need to see captured)"),
+                      ("_iso", "NSDP_WGRAD_STREAM=0 python bench.py --full --eager --reps 1 --steps 5 --warmup 2 --no-cpu-baseline "
                                "(weight gradients on the main stream: every duration is the kernel alone -- the profile "
                                "that matches bench.py's `roofline`)"),
-                      ("_replay", "python bench.py --reps 1 --steps 5 --warmup 2 --no-cpu-baseline (the DEFAULT launcher: the captured "
+                      ("_replay", "python bench.py --full --reps 1 --steps 5 --warmup 2 --no-cpu-baseline (the DEFAULT launcher: the captured "
                                   "step replayed by the multi-stream graph executor, traced as it runs -- durations include the "
                                   "time a kernel shares the chip with the other stream's kernel)"),
-                      ("_bf16", "NSDP_WGRAD_STREAM=0 python bench.py --dtype bf16 --workload arbitrary_train --steps 5 "
+                      ("_bf16", "NSDP_WGRAD_STREAM=0 python bench.py --full --dtype bf16 --workload arbitrary_train --steps 5 "
                                 "--warmup 2 --no-cpu-baseline (BASELINE config 3: FlowArbitrary, bf16 storage)")):
-    stats = os.path.join(root, "gpurun_out", f"prof_{tag}{suffix}", f"{tag}{suffix}_kernel_stats.csv")
+    stats = os.path.join(src_dir, f"prof_{tag}{suffix}", f"{tag}{suffix}_kernel_stats.csv")
     if not os.path.exists(stats):
         continue
     rows = list(csv.DictReader(open(stats)))
@@ -56,7 +57,7 @@ for suffix, title in (("", "python bench.py --eager --reps 1 --steps 5 --warmup 
 for pmc_suffix, pmc_what in (("", "the default workload"), ("_bf16", "--dtype bf16")):
     pmc = {}
     for key, sub, pre in (("FETCH_SIZE", "pmc_fetch" + pmc_suffix, "f"), ("WRITE_SIZE", "pmc_write" + pmc_suffix, "w")):
-        path = os.path.join(root, "gpurun_out", sub, f"{pre}_counter_collection.csv")
+        path = os.path.join(src_dir, sub, f"{pre}_counter_collection.csv")
         if not os.path.exists(path):
             continue
         agg = collections.defaultdict(lambda: [0, 0.0, 0.0])
@@ -72,7 +73,7 @@ for pmc_suffix, pmc_what in (("", "the default workload"), ("_bf16", "--dtype bf
         names = sorted(set().union(*[set(v) for v in pmc.values()]),
                        key=lambda n: -sum(pmc[k][n][1] for k in pmc if n in pmc[k]))
         with open(os.path.join(out_dir, f"{tag}_pmc_hbm{pmc_suffix}.md"), "w") as f:
-            f.write(f"# rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes), bench.py --steps 1 --warmup 1 (B = 32, {pmc_what})\n\n")
+            f.write(f"# rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes), bench.py --full --steps 1 --warmup 1 (B = 32, {pmc_what})\n\n")
             f.write("Counter unit = KiB as reported.  On gfx950 FETCH_SIZE under-reports wide coalesced reads by 2x\n"
                     "(MI355X_MICROARCH.md, HBM section): the `fetch x2` column applies that correction.\n\n")
             f.write("| kernel | launches | FETCH_SIZE sum KiB | fetch x2 MiB | WRITE_SIZE sum KiB | max launch fetch KiB | max launch write KiB |\n|---|---:|---:|---:|---:|---:|---:|\n")
@@ -83,7 +84,7 @@ for pmc_suffix, pmc_what in (("", "the default workload"), ("_bf16", "--dtype bf
         json.dump({k: {n: v for n, v in agg.items()} for k, agg in pmc.items()},
                   open(os.path.join(out_dir, f"{tag}_pmc_hbm{pmc_suffix}.json"), "w"), indent=0)
 # SQ counters (one pass, NSDP_WGRAD_STREAM=0 so that counters are per kernel): matrix-pipe busy fraction and wait split
-sq_path = os.path.join(root, "gpurun_out", "pmc_sq", "s_counter_collection.csv")
+sq_path = os.path.join(src_dir, "pmc_sq", "s_counter_collection.csv")
 if os.path.exists(sq_path):
     agg = collections.defaultdict(lambda: collections.defaultdict(float))
     launches = collections.Counter()
@@ -99,7 +100,7 @@ if os.path.exists(sq_path):
     with open(os.path.join(out_dir, f"{tag}_pmc_mfma.md"), "w") as f:
         f.write("# rocprofv3 --pmc SQ_WAVE_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY "
                 "GRBM_GUI_ACTIVE --kernel-trace (one pass, no other trace domains): NSDP_WGRAD_STREAM=0 python bench.py "
-                "--steps 1 --warmup 1 --no-cpu-baseline, B=32\n\n")
+                "--full --steps 1 --warmup 1 --no-cpu-baseline, B=32\n\n")
         f.write("MFMA busy = SQ_VALU_MFMA_BUSY_CYCLES / (GRBM_GUI_ACTIVE/8 x 1024 SIMDs): fraction of all SIMD cycles of the "
                 "kernel's lifetime in which the matrix pipe is busy.  A bf16 16x16x32 MFMA is busy 16 cycles and an fp32 "
                 "16x16x4 MFMA 32 cycles, so this is the fraction of the dense MFMA peak of the kernel's data type at the "
@@ -119,7 +120,7 @@ for name in ("bench_default.json", "bench_b8.json", "bench_arbitrary.json", "ben
              "bench_arbitrary_bf16_eager.json", "bench_force_reducer_nccl.json", "bench_arbitrary_bf16_net1f32.json",
              "bench_force_reducer_nccl_overlap.json", "bench_arbitrary_bf16_net1dec32.json", "bench_8ranks_gloo.json",
              "linear_shapes.txt", "x3_operands.json"):
-    src = os.path.join(root, "gpurun_out", f"{tag}_{name}")       # written by tools/profile_round.sh
+    src = os.path.join(src_dir, f"{tag}_{name}")       # written by tools/profile_round.sh
     if os.path.exists(src) and open(src).read().strip():
         open(os.path.join(out_dir, f"{tag}_{name}"), "w").write(open(src).read())
 print("wrote", sorted(os.listdir(out_dir)))

@@ -1,6 +1,6 @@
 """Timeline of a replayed train step from a rocprofv3 kernel trace: per queue (= HIP stream) busy time, the overlap between
 queues, idle gaps of the busiest queue, and what the other queue ran during the last millisecond before each optimizer step.
-    rocprofv3 --kernel-trace --output-format csv -d DIR -o t -- python bench.py --reps 1 --steps 5 --warmup 2 --no-cpu-baseline
+    rocprofv3 --kernel-trace --output-format csv -d DIR -o t -- python bench.py --full --reps 1 --steps 5 --warmup 2 --no-cpu-baseline
     python tools/timeline.py DIR/**/t_kernel_trace.csv [--steps 5]"""
 import argparse
 import csv
