@@ -1,0 +1,165 @@
+"""Dense inference of one batch of shapes split over GPUs by query point (nsdp_amd.query_shard), timed.
+
+    python -m nsdp_amd.infer CONFIG --gpus N [--backend nccl|gloo] [--batch B] [--surface NS] [--queries NQ]
+                             [--steps K] [--warmup W] [--graph] [--weight_file F] [--out DIR]
+
+Every rank builds the model of the config (forward / backward / arbitrary; procedural weights, or ``--weight_file``), the same
+synthetic batch (``synth.make_batch`` with one seed for all ranks: the ranks decode the same shapes) and runs the reference's
+``test_on_batch`` through ``query_sharded``: surface samples and NQ mesh vertices per shape, encoded on every rank, decoded in
+slices, all-gathered.  ``--gpus 1`` runs the same wrapper at world 1 -- no process group, the gather is the identity -- as the
+A/B point (the same work as the unwrapped ``test_on_batch``).  From a bare shell the N ranks are launched here
+(torch.distributed.run on 127.0.0.1, rank r -> GPU r, as nsdp_amd.train); under torchrun this process is one of them.
+
+Rank 0 prints one JSON line: ``ms_per_call`` (HIP events around K calls after W warm-ups, the gather included; the maximum over
+ranks), query points per second (the B x NQ vertices, as bench.py's dense_inference counts them; the surface samples' decode is
+in the time), ``world``, ``backend``, the all-gather form used, each rank's device and PCI address and its calls that replayed /
+ran eagerly, and ``ranks_agree`` (every rank's gathered predictions have the same byte checksum).  ``--out DIR`` writes rank 0's
+predictions as DIR/<key>.npy.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+
+SEED_DATA, SEED_WEIGHTS = 1000, 2048      # (bench.py's procedural weights; one batch for every rank)
+KEYS = ("surface_samples_tgt_pred", "verts_tgt_pred")
+
+
+def _checksum(t) -> int:
+    """int64 sum over the int32 view: equal sums for bit-equal fp32 tensors."""
+    import torch
+    return int(t.contiguous().view(torch.int32).to(torch.int64).sum())
+
+
+def _pyramid(config, ns):
+    """The encoder samples at most the points it has: every level of npoints_per_layer capped at the level above it."""
+    kw = config["model"]["encoder_kwargs"]
+    levels, prev = [], int(ns)
+    for p in kw["npoints_per_layer"]:
+        prev = min(int(p), prev)
+        levels.append(prev)
+    kw["npoints_per_layer"] = levels
+
+
+def main(argv=None):
+    argv = list(sys.argv[1:] if argv is None else argv)
+    ap = argparse.ArgumentParser(description="Dense inference split over GPUs by query point")
+    ap.add_argument("config_file")
+    ap.add_argument("--gpus", type=int, default=1, help="ranks, one process per GPU; the query points are split over them")
+    ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
+                    help="torch.distributed backend (nccl = RCCL; gloo to exercise several ranks on one GPU)")
+    ap.add_argument("--batch", type=int, default=None, help="shapes per call (default: the config's test.batch_size, else 1)")
+    ap.add_argument("--surface", type=int, default=None,
+                    help="surface samples per shape (default: the config's data.num_surf_samples, else the encoder's first level)")
+    ap.add_argument("--queries", type=int, default=100000, help="mesh vertices per shape (default 100000, BASELINE config 5)")
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--graph", action="store_true",
+                    help="capture each rank's encode and local decode once and replay it; the gather runs eagerly after the replay")
+    ap.add_argument("--weight_file", default=None, help="weights of the whole model (default: procedural weights)")
+    ap.add_argument("--out", default=None, help="directory for rank 0's predictions (<key>.npy)")
+    args = ap.parse_args(argv)
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
+        from .train import launch_ranks
+        return launch_ranks(args.gpus, argv, module="nsdp_amd.infer")
+    if args.gpus != world:
+        sys.exit(f"nsdp_amd.infer: --gpus {args.gpus} but the launcher's WORLD_SIZE is {world}")
+    rank, local_rank = int(os.environ.get("RANK", "0")), int(os.environ.get("LOCAL_RANK", "0"))
+    local_world = int(os.environ.get("LOCAL_WORLD_SIZE", str(world)))
+    from .cpu_budget import cap_thread_pools
+    cap_thread_pools(max(1, 16 // max(1, local_world)))
+    import numpy as np
+    import torch
+    import torch.distributed as dist
+    if not torch.cuda.is_available():
+        sys.exit("nsdp_amd.infer: needs a GPU (the decode has no CPU path)")
+    if world > 1:
+        from .parallel import rank_device
+        index, cpus = rank_device(local_rank, world, args.backend)       # rank r -> GPU r, pinned to its CPU slice
+        device = torch.device("cuda", index)
+        print(f"nsdp_amd.infer: rank {rank} -> GPU {index}, CPUs {cpus}", file=sys.stderr)
+        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+        if args.backend == "nccl":
+            dist.init_process_group("nccl", rank=rank, world_size=world, device_id=device)
+        else:
+            dist.init_process_group(args.backend, rank=rank, world_size=world)
+    else:
+        index = 0
+        device = torch.device("cuda", index)
+        torch.cuda.set_device(index)
+
+    from . import synth
+    from .config import load_config
+    from .model import build_model
+    from .query_shard import QueryShards, query_sharded
+    config = load_config(args.config_file)
+    batch = args.batch or int(config.get("test", {}).get("batch_size", 1) or 1)
+    ns = args.surface or int(config.get("data", {}).get("num_surf_samples", 0) or
+                             config["model"]["encoder_kwargs"]["npoints_per_layer"][0])
+    nq = int(args.queries)
+    _pyramid(config, ns)
+    model, _, _, test_fn = build_model(config, weight_file=args.weight_file, device="cpu")
+    if args.weight_file is None:
+        state = synth.procedural_state_dict(model.state_dict(), SEED_WEIGHTS)
+        model.load_state_dict({k: torch.from_numpy(v) for k, v in state.items()})
+    model.to(device).eval()
+    data = synth.make_batch(SEED_DATA, batch, ns, nq)
+    dd = {k: torch.from_numpy(np.ascontiguousarray(v)).to(device) for k, v in data.items()}
+    dd["surface_samples_src"] = dd["surface_samples_inputs"][:, :, 0:3].contiguous()
+    dd["verts_src"], dd["verts_tgt"] = dd.pop("space_samples_src"), dd.pop("space_samples_tgt")
+
+    shards = QueryShards(rank, world)
+    step = query_sharded(test_fn, shards, graph=args.graph)
+
+    def fence():
+        torch.cuda.synchronize()
+        if world > 1:
+            dist.barrier()
+
+    for _ in range(max(args.warmup, 1 if args.graph else 0)):      # (--graph: the first call captures)
+        step(model, dd, config)
+    fence()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(args.steps):
+        step(model, dd, config)
+    e1.record()
+    torch.cuda.synchronize()
+    ms = e0.elapsed_time(e1) / max(1, args.steps)
+
+    props = torch.cuda.get_device_properties(index)
+    mine = {"rank": rank, "device_index": index, "pci_domain_id": getattr(props, "pci_domain_id", None),
+            "pci_bus_id": getattr(props, "pci_bus_id", None), "hip_visible_devices": os.environ.get("HIP_VISIBLE_DEVICES"),
+            "ms_per_call": round(ms, 4), "replays": step.replays, "eager_calls": step.eager_calls,
+            "checksums": [_checksum(dd[k]) for k in KEYS]}
+    ranks = [None] * world
+    if world > 1:
+        dist.all_gather_object(ranks, mine)
+    else:
+        ranks = [mine]
+    if rank == 0:
+        if args.out:
+            os.makedirs(args.out, exist_ok=True)
+            for k in KEYS:
+                np.save(os.path.join(args.out, k + ".npy"), dd[k].cpu().numpy())
+        ms_max = max(r["ms_per_call"] for r in ranks)
+        line = {"metric": "dense_inference_query_sharded", "model_type": config["model"]["type"], "world": world,
+                "backend": args.backend if world > 1 else None, "graph": bool(args.graph), "batch": batch, "surface": ns,
+                "queries": nq, "steps": args.steps, "warmup": args.warmup, "ms_per_call": ms_max,
+                "query_points_per_s": round(batch * nq / (ms_max / 1e3), 1) if ms_max > 0 else None,
+                "gather": None if world == 1 else ("all_gather" if shards.list_form else "all_gather_into_tensor"),
+                "ranks_agree": all(r["checksums"] == ranks[0]["checksums"] for r in ranks),
+                "ranks_share_a_device": len({(r["pci_domain_id"], r["pci_bus_id"]) for r in ranks}) < world,
+                "ranks": [{k: r[k] for k in ("rank", "device_index", "pci_domain_id", "pci_bus_id", "hip_visible_devices",
+                                             "ms_per_call", "replays", "eager_calls")} for r in ranks]}
+        print(json.dumps(line), flush=True)
+    if world > 1:
+        dist.destroy_process_group()
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main(sys.argv[1:]))

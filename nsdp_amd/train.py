@@ -151,9 +151,10 @@ def initial_weight_files(config, args=None):
     return tuple(out)
 
 
-def launch_ranks(n, argv):
+def launch_ranks(n, argv, module="nsdp_amd.train"):
     """``python -m nsdp_amd.train ... --gpus N`` from a bare shell: start the N ranks through torch.distributed.run on
-    127.0.0.1 and a free port (rank r -> GPU r); the children see RANK / WORLD_SIZE and take the worker path of main()."""
+    127.0.0.1 and a free port (rank r -> GPU r); the children see RANK / WORLD_SIZE and take the worker path of main().
+    ``module``: the entry point the ranks run (nsdp_amd.infer launches its ranks the same way)."""
     import socket
     import subprocess
     with socket.socket() as sock:
@@ -163,7 +164,7 @@ def launch_ranks(n, argv):
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")     # dmabuf IPC: what RCCL needs on this driver
     env.setdefault("OMP_NUM_THREADS", str(max(1, 16 // n)))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), "-m", "nsdp_amd.train"] + list(argv)
+           "--master-port", str(port), "-m", module] + list(argv)
     return subprocess.call(cmd, env=env)
 
 
