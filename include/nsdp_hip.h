@@ -552,6 +552,19 @@ int nsdp_decoder_fused_fwd(const float *xyz_q, const float *anchors, const int32
                            const float *const *weights, int n_weights, int B, int NQ, int A, int KN, int D,
                            int H, float *out, void *stream);
 
+/* The same decoder with bf16 MFMA operands (ABI version 8; opt-in, a different numerical contract): the arguments of
+ * nsdp_decoder_fused_fwd, but every W of weights[17] is bf16, rounded to nearest even, in the fragment-major order
+ * [out tile of 16][k block kb of 32 = tiles 2 kb, 2 kb + 1][lane = 16 g + li][8] holding
+ *   W_rowmajor[16 tile + li][16 (2 kb) + 4 g + j] for j < 4 and W_rowmajor[16 tile + li][16 (2 kb + 1) + 4 g + (j - 4)] for j >= 4;
+ * an odd number of input tiles (208 = 13) ends each out tile with a half block [lane][4] of the last tile alone, so one
+ * out tile is (input tiles) x 512 bytes.  fc_delta.0 (weights[0]) and every bias stay fp32 as above.  Only the matrix
+ * operands are rounded (these weights and the activation entering each of these layers); accumulators, biases, tables,
+ * softmax state, the residual stream and the output are fp32.  A row's result does not depend on the rows around it. */
+int nsdp_decoder_fused_fwd_bf16(const float *xyz_q, const float *anchors, const int32_t *idx, const float *qk,
+                                const float *vtab, const float *a_g, const float *v_g,
+                                const void *const *weights, int n_weights, int B, int NQ, int A, int KN, int D,
+                                int H, float *out, void *stream);
+
 /* ----------------------------------------------------------------------------------------------
  * BatchNorm1d on channels-last rows x[R,C] (R = B*n, C % 4 == 0, C <= 1024), replacing the 35
  * nn.BatchNorm1d calls of the encoder (model/encoder/blocks.py:132, :158, :300-312) together with the

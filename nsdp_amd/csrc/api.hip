@@ -52,7 +52,7 @@ const char *kind_name(int kind) {
                                          "knn_kernel",        "gather_rows_kernel",  "scatter_add_rows_kernel",
                                          "attn_fwd_kernels",  "attn_bwd_kernels",    "batch_norm_kernels",
                                          "decoder_fwd_kernel", "linear_bf16x3_kernel", "wgrad_bf16x3_kernel",
-                                         "linear_bf16_kernel", "wgrad_bf16_kernel"};
+                                         "linear_bf16_kernel", "wgrad_bf16_kernel", "decoder_fwd_bf16_kernel"};
   return (kind >= 0 && kind < kNumKinds) ? names[kind] : "?";
 }
 
@@ -94,7 +94,7 @@ Scope::~Scope() {
 
 extern "C" {
 
-int nsdp_abi_version(void) { return 7; }
+int nsdp_abi_version(void) { return 8; }
 
 const char *nsdp_last_error(void) { return nsdp::g_last_error; }
 

@@ -21,6 +21,7 @@ enum Kind {
   kWgradX3,      // wgrad_bf16x3_kernel + its reduce
   kLinearB16,    // linear_bf16_kernel (bf16 storage, one bf16 MFMA product)
   kWgradB16,     // wgrad_bf16_kernel + its reduce
+  kDecoderFwdB16,  // fused decoder forward with bf16 MFMA operands (decoder_fused_fwd_bf16_kernel)
   kNumKinds
 };
 

@@ -8,16 +8,64 @@ kernel launch.  There is no fallback: shapes the kernel was not built for raise.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 
 import torch
 import torch.nn.functional as F
 
-from . import _lib, hip_linear, pointnet2_utils
+from . import _lib, hip_linear, pointnet2_utils, precision
 
 import os
 
 ENABLED = os.environ.get("NSDP_FUSED_DECODER", "1") != "0"   # off: the layer-by-layer kernels (debug / A-B timing)
+MODES = ("f32", "bf16")
+
+
+def _check_mode(name) -> str:
+    if name not in MODES:
+        raise ValueError(f"fused decoder dtype must be one of {MODES}, got {name!r}")
+    return name
+
+
+# Operand type of the fused kernel's matrix products.  "f32": nsdp_decoder_fused_fwd (the default, pinned to the oracle at 1e-4).
+# "bf16": nsdp_decoder_fused_fwd_bf16 -- weights and layer inputs rounded to bf16 as MFMA operands only, everything else fp32;
+# a different numerical contract (about 0.4 % relative on the decoder output), taken in either storage mode.  Read when a
+# forward runs, so a captured graph (graph_step) keeps the kernel it was captured with.
+MODE = _check_mode(os.environ.get("NSDP_FUSED_DECODER_DTYPE", "f32"))
+# FlowArbitrary under MODE "bf16": network 1's decoder -- whose per-point outputs are the coordinates network 2 samples, groups
+# and searches, so that its error is amplified by those discrete selections (nsdp_amd/precision.py, NSDP_BF16_NET1) -- keeps the
+# fp32 kernel and only network 2's decoder takes the bf16-operand one.  "bf16": both do.
+NET1_MODE = _check_mode(os.environ.get("NSDP_FUSED_DECODER_NET1", "f32"))
+
+
+def set_mode(name: str) -> None:
+    global MODE
+    MODE = _check_mode(name)
+
+
+@contextlib.contextmanager
+def mode(name: str):
+    """``with hip_decoder.mode("bf16"): ...`` -- the fused decoder's operand type inside the block, restored after it."""
+    global MODE
+    prev, MODE = MODE, _check_mode(name)
+    try:
+        yield
+    finally:
+        MODE = prev
+
+
+def canonicalize_mode():
+    """The context FlowArbitrary decodes its first network in (see NET1_MODE)."""
+    return mode("f32") if (MODE == "bf16" and NET1_MODE == "f32") else contextlib.nullcontext()
+
+
+def fused_for_inference() -> bool:
+    """Does the no-grad forward of a supported decoder take a fused kernel?  The fp32 kernel needs fp32 storage (under bf16
+    storage the layered bf16 path runs); the bf16-operand kernel is taken in either storage mode."""
+    return ENABLED and (MODE == "bf16" or not precision.is_bf16())
+
+
 DIM, HIDDEN, NBLOCKS, OUT = 200, 128, 5, 3
 DP, HP = 208, 128            # channel counts padded to multiples of 16 (one MFMA tile)
 
@@ -40,6 +88,22 @@ def _frag(w):
     return w.view(to, 16, ti, 4, 4).permute(0, 2, 3, 1, 4).contiguous()
 
 
+def _frag_bf16(w):
+    """Row-major zero-padded [16*To, 16*Ti] -> the bf16 A-operand pack of nsdp_decoder_fused_fwd_bf16, [To, Ti*256] bf16
+    (rounded to nearest even).  Per out tile: k blocks of two input tiles (2 kb, 2 kb + 1) as [lane = 16 g + li][8], element
+    j < 4 = W[16 to + li][16 (2 kb) + 4 g + j], j >= 4 = W[16 to + li][16 (2 kb + 1) + 4 g + (j - 4)] -- hardware slot
+    k = 8 g + j of v_mfma_f32_16x16x32_bf16, whose B operand in the same slot is the converted accumulator (tile, register
+    j & 3) of the previous layer; then, for odd Ti, the last tile alone as [lane][4] (k = 4 g + j of the K = 16 instruction)."""
+    to, ti = w.shape[0] // 16, w.shape[1] // 16
+    wv = w.to(torch.bfloat16).view(to, 16, ti, 4, 4)                  # [to, li, tile, g, j]
+    pairs = ti // 2
+    parts = [wv[:, :, :2 * pairs].reshape(to, 16, pairs, 2, 4, 4)     # [to, li, kb, half, g, j]
+             .permute(0, 2, 4, 1, 3, 5).reshape(to, pairs * 512)]      # [to, kb, g, li, half, j]
+    if ti & 1:
+        parts.append(wv[:, :, ti - 1].permute(0, 2, 1, 3).reshape(to, 256))   # [to, g, li, j]
+    return torch.cat(parts, dim=1).contiguous()
+
+
 def _pad1(b, n):
     return F.pad(b, (0, n - b.shape[0])).contiguous()
 
@@ -48,7 +112,8 @@ class _Pack:
     """Zero-padded copies of the decoder weights in the layout of include/nsdp_hip.h, rebuilt whenever a
     parameter changes (optimizer steps bump ``_version``; load_state_dict copies in place and bumps it too)."""
 
-    def __init__(self):
+    def __init__(self, frag=_frag):
+        self.frag = frag            # _frag: fp32 packs; _frag_bf16: the permuted bf16 packs of the bf16-operand kernel
         self.key = None
         self.tensors = None
         self.ptrs = None
@@ -61,6 +126,7 @@ class _Pack:
         if key == self.key:
             return self
         ct = dec.ct1
+        _frag = self.frag
         with torch.no_grad():
             d0, d2 = ct.fc_delta[0], ct.fc_delta[2]
             g0, g2 = ct.fc_gamma[0], ct.fc_gamma[2]
@@ -100,17 +166,23 @@ def decoder_forward(dec, xyz_q: torch.Tensor, encoding: dict) -> torch.Tensor:
     z, anchors, feats = encoding["z"], encoding["anchors"], encoding["anchor_feats"]
     if z.dim() != 2:
         raise _lib.NsdpHipError("fused decoder: per-query latent codes are not used by any NSDP configuration")
-    pack = dec.__dict__.get("_fused_pack")
+    bf16 = MODE == "bf16"
+    slot = "_fused_pack_bf16" if bf16 else "_fused_pack"
+    pack = dec.__dict__.get(slot)
     if pack is None:
-        pack = dec.__dict__["_fused_pack"] = _Pack()
+        pack = dec.__dict__[slot] = _Pack(_frag_bf16 if bf16 else _frag)
     pack = pack.get(dec)
+    # bf16 storage (bf16-operand mode only): the encoding is upcast and the per-shape tables are built by the fp32 kernels
+    tables_f32 = precision.storage(torch.float32) if precision.is_bf16() else contextlib.nullcontext()
+    if precision.is_bf16():
+        z, feats = z.float(), feats.float()
     ct = dec.ct1
     B, NQ, _ = xyz_q.shape
     A = anchors.shape[1]
     xyz_q_in = xyz_q
     xyz_q = xyz_q.contiguous().float()
     anchors = anchors.contiguous().float()
-    with torch.no_grad(), _lib.on_device(xyz_q):
+    with torch.no_grad(), _lib.on_device(xyz_q), tables_f32:
         idx = encoding.get("query_idx") if encoding.get("query_points") is xyz_q_in else None      # (searched ahead: Deformation_Networks.geometry)
         if idx is None:
             idx = pointnet2_utils.knn(xyz_q, anchors, ct.nneigh)                # [B,NQ,k] int32
@@ -126,9 +198,10 @@ def decoder_forward(dec, xyz_q: torch.Tensor, encoding: dict) -> torch.Tensor:
         h = lin(q - k_g, pack.gamma_rows[0], t[4], relu_out=True)               # global-token logits
         a_g = lin(h, pack.gamma_rows[1], t[6]).contiguous()
         out = torch.empty(B, NQ, OUT, dtype=torch.float32, device=xyz_q.device)
-        _lib.check(_lib.lib().nsdp_decoder_fused_fwd(
+        name = "nsdp_decoder_fused_fwd_bf16" if bf16 else "nsdp_decoder_fused_fwd"
+        _lib.check(getattr(_lib.lib(), name)(
             _lib.fptr(xyz_q, "xyz_q"), _lib.fptr(anchors, "anchors"), _lib.iptr(idx, "idx"),
             _lib.fptr(qk, "qk"), _lib.fptr(vtab, "vtab"), _lib.fptr(a_g, "a_g"), _lib.fptr(v_g, "v_g"),
             pack.ptrs, len(t), B, NQ, A, ct.nneigh, DIM, HIDDEN, _lib.fptr(out, "out"), _lib.stream_ptr()),
-            "nsdp_decoder_fused_fwd")
+            name)
     return out

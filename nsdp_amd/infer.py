@@ -1,7 +1,7 @@
 """Dense inference of one batch of shapes split over GPUs by query point (nsdp_amd.query_shard), timed.
 
     python -m nsdp_amd.infer CONFIG --gpus N [--backend nccl|gloo] [--batch B] [--surface NS] [--queries NQ]
-                             [--steps K] [--warmup W] [--graph] [--weight_file F] [--out DIR]
+                             [--steps K] [--warmup W] [--graph] [--weight_file F] [--out DIR] [--decoder-dtype f32|bf16]
 
 Every rank builds the model of the config (forward / backward / arbitrary; procedural weights, or ``--weight_file``), the same
 synthetic batch (``synth.make_batch`` with one seed for all ranks: the ranks decode the same shapes) and runs the reference's
@@ -14,7 +14,9 @@ Rank 0 prints one JSON line: ``ms_per_call`` (HIP events around K calls after W 
 ranks), query points per second (the B x NQ vertices, as bench.py's dense_inference counts them; the surface samples' decode is
 in the time), ``world``, ``backend``, the all-gather form used, each rank's device and PCI address and its calls that replayed /
 ran eagerly, and ``ranks_agree`` (every rank's gathered predictions have the same byte checksum).  ``--out DIR`` writes rank 0's
-predictions as DIR/<key>.npy.
+predictions as DIR/<key>.npy.  ``--decoder-dtype bf16`` selects the fused decoder's bf16-operand kernel on every rank
+(hip_decoder.MODE; ``decoder_dtype`` in the line); one extra call with the fp32 kernel after the timed region then gives
+``max_abs_diff_vs_f32`` and ``l2_vs_f32`` (max over shapes of the RMS point distance) of the mesh-vertex predictions.
 """
 from __future__ import annotations
 
@@ -43,8 +45,7 @@ def _pyramid(config, ns):
     kw["npoints_per_layer"] = levels
 
 
-def main(argv=None):
-    argv = list(sys.argv[1:] if argv is None else argv)
+def build_parser():
     ap = argparse.ArgumentParser(description="Dense inference split over GPUs by query point")
     ap.add_argument("config_file")
     ap.add_argument("--gpus", type=int, default=1, help="ranks, one process per GPU; the query points are split over them")
@@ -60,6 +61,14 @@ def main(argv=None):
                     help="capture each rank's encode and local decode once and replay it; the gather runs eagerly after the replay")
     ap.add_argument("--weight_file", default=None, help="weights of the whole model (default: procedural weights)")
     ap.add_argument("--out", default=None, help="directory for rank 0's predictions (<key>.npy)")
+    ap.add_argument("--decoder-dtype", default=None, choices=["f32", "bf16"],
+                    help="operand type of the fused decoder kernel on every rank (default: NSDP_FUSED_DECODER_DTYPE, else f32)")
+    return ap
+
+
+def main(argv=None):
+    argv = list(sys.argv[1:] if argv is None else argv)
+    ap = build_parser()
     args = ap.parse_args(argv)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -91,7 +100,9 @@ def main(argv=None):
         device = torch.device("cuda", index)
         torch.cuda.set_device(index)
 
-    from . import synth
+    from . import hip_decoder, synth
+    if args.decoder_dtype is not None:
+        hip_decoder.set_mode(args.decoder_dtype)
     from .config import load_config
     from .model import build_model
     from .query_shard import QueryShards, query_sharded
@@ -135,6 +146,17 @@ def main(argv=None):
             "pci_bus_id": getattr(props, "pci_bus_id", None), "hip_visible_devices": os.environ.get("HIP_VISIBLE_DEVICES"),
             "ms_per_call": round(ms, 4), "replays": step.replays, "eager_calls": step.eager_calls,
             "checksums": [_checksum(dd[k]) for k in KEYS]}
+    vs_f32 = {}
+    if hip_decoder.MODE == "bf16":
+        # one eager call with the fp32 kernel, outside the timed region (every rank: the gather is collective)
+        pred = {k: dd[k].clone() for k in KEYS}
+        with hip_decoder.mode("f32"):
+            query_sharded(test_fn, shards)(model, dd, config)
+        if rank == 0:
+            d = pred["verts_tgt_pred"].double() - dd["verts_tgt_pred"].double()
+            vs_f32 = {"max_abs_diff_vs_f32": float(d.abs().max()),
+                      "l2_vs_f32": float(d.pow(2).sum(-1).mean(-1).sqrt().max())}
+        dd.update(pred)
     ranks = [None] * world
     if world > 1:
         dist.all_gather_object(ranks, mine)
@@ -148,7 +170,8 @@ def main(argv=None):
         ms_max = max(r["ms_per_call"] for r in ranks)
         line = {"metric": "dense_inference_query_sharded", "model_type": config["model"]["type"], "world": world,
                 "backend": args.backend if world > 1 else None, "graph": bool(args.graph), "batch": batch, "surface": ns,
-                "queries": nq, "steps": args.steps, "warmup": args.warmup, "ms_per_call": ms_max,
+                "queries": nq, "steps": args.steps, "warmup": args.warmup, "decoder_dtype": hip_decoder.MODE,
+                **vs_f32, "ms_per_call": ms_max,
                 "query_points_per_s": round(batch * nq / (ms_max / 1e3), 1) if ms_max > 0 else None,
                 "gather": None if world == 1 else ("all_gather" if shards.list_form else "all_gather_into_tensor"),
                 "ranks_agree": all(r["checksums"] == ranks[0]["checksums"] for r in ranks),

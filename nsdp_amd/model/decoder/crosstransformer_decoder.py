@@ -29,7 +29,7 @@ class CrossTransformerDecoder(nn.Module):
     def prefetch(self, xyz_q, anchors, after=None):
         """CrossTransformerBlock.prefetch for this decoder's attention block (None where forward() would not use it: the
         no-grad path runs the fused whole-decoder kernel)."""
-        if (hip_decoder.ENABLED and not torch.is_grad_enabled() and hip_decoder.supported(self) and not precision.is_bf16()):
+        if hip_decoder.fused_for_inference() and not torch.is_grad_enabled() and hip_decoder.supported(self):
             return None
         return self.ct1.prefetch(xyz_q, anchors, after)
 
@@ -45,9 +45,9 @@ class CrossTransformerDecoder(nn.Module):
         return {"query_idx": ops.knn_indices(xyz_q, anchors, self.ct1.nneigh)}
 
     def forward(self, xyz_q, encoding):
-        if (hip_decoder.ENABLED and not torch.is_grad_enabled() and hip_decoder.supported(self)
-                and not precision.is_bf16()):
-            # inference: kNN + one fused kernel (18 dense layers + softmax in registers), nsdp_decoder_fused_fwd
+        if hip_decoder.fused_for_inference() and not torch.is_grad_enabled() and hip_decoder.supported(self):
+            # inference: kNN + one fused kernel (18 dense layers + softmax in registers), nsdp_decoder_fused_fwd; with
+            # hip_decoder.MODE == "bf16" its bf16-operand form, in either storage mode
             return hip_decoder.decoder_forward(self, xyz_q, encoding)
         lat = self.ct1(xyz_q, encoding["z"], encoding["anchors"], encoding["anchor_feats"], prefetched=encoding.get("prefetch"),
                        idx=self._query_idx(xyz_q, encoding))

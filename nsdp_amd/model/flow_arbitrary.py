@@ -7,7 +7,7 @@ import contextlib
 import torch
 import torch.nn as nn
 
-from .. import hip_batchnorm, precision
+from .. import hip_batchnorm, hip_decoder, precision
 from . import deformation_networks
 from .utils import compute_l2_error
 
@@ -35,7 +35,7 @@ class FlowArbitrary(nn.Module):
         updates from the same batch statistics, num_batches_tracked += 2 -- which hip_batchnorm.running_updates reproduces.
         Autograd sums the decoder paths into one encoder backward."""
         net = self.model_canonicalize
-        with self._canonicalize_storage():
+        with self._canonicalize_storage(), hip_decoder.canonicalize_mode():
             if not deformation_networks.ENCODE_ONCE:
                 return [net(q, surface_samples_src) for q in query_sets]
             queries = query_sets[0] if len(query_sets) == 1 else torch.cat(list(query_sets), dim=1)
