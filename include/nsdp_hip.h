@@ -119,6 +119,19 @@ int nsdp_three_interpolate_grad(const float *grad_out, const int32_t *idx, const
 int nsdp_knn(const float *query, const float *source, int B, int n, int m, int k, int32_t *idx_out,
              float *dist2_out, void *stream);
 
+/* Packed ("ragged") query sets (ABI version 9): the rows of B shapes of different sizes concatenated, packed(cap,C), with
+ * offsets(B+1) i32 ON THE DEVICE -- offsets[0] = 0, shape b owns rows offsets[b] .. offsets[b+1], offsets[B] = total <= cap.
+ * Rows at or beyond total are padding: never read as results, never written.  The host passes only `cap` and `B` (they fix the
+ * launch grid) and never reads `offsets`, so one captured graph serves every batch of B shapes whose rows sum to at most
+ * cap.  Every entry of `offsets` is clamped to [previous entry, cap] as the kernels read it: whatever it holds, no access
+ * leaves rows [0, cap) and shapes [0, B) -- a corrupt offsets tensor gives wrong numbers, not a fault.
+ *
+ * nsdp_knn over a packed query set: query(cap,3), source(B,m,3) -> idx(cap,k), dist2_out(cap,k) or NULL.  The
+ * one-lane-per-query kernel (the decoder's case, m = 100 anchors, k = 7), a 256-query workgroup belongs to one shape; the
+ * arithmetic and the (distance, index) order are nsdp_knn's, so a row gets the bits nsdp_knn gives it on its shape alone. */
+int nsdp_knn_ragged(const float *query, const int32_t *offsets, const float *source, int B, int cap, int m, int k,
+                    int32_t *idx_out, float *dist2_out, void *stream);
+
 /* index_points(points(B,N,C), idx(B,S)) -> (B,S,C) (row gather; model/utils.py:58-70) */
 int nsdp_gather_rows(const float *points, const int32_t *idx, int B, int N, int C, int S, float *out,
                      void *stream);
@@ -564,6 +577,20 @@ int nsdp_decoder_fused_fwd_bf16(const float *xyz_q, const float *anchors, const 
                                 const float *vtab, const float *a_g, const float *v_g,
                                 const void *const *weights, int n_weights, int B, int NQ, int A, int KN, int D,
                                 int H, float *out, void *stream);
+
+/* Both decoders over a packed query set (ABI version 9, see nsdp_knn_ragged for the layout): xyz_q (cap,3), idx (cap,KN),
+ * out (cap,3), offsets (B+1) on the device; the per-shape tables and the weights as in the rectangular entry points.  A
+ * 16-query wave tile belongs to one shape; a shape's last tile is partial (lanes clamped to the shape's last row, not
+ * stored) -- the same kernel body as the rectangular form, so a row gets the bits the rectangular call gives it.  Anchor
+ * indices are clamped to [0, A).  Profiling accounts FLOPs / bytes with cap (an upper bound: the host does not know total). */
+int nsdp_decoder_fused_fwd_ragged(const float *xyz_q, const int32_t *offsets, const float *anchors, const int32_t *idx,
+                                  const float *qk, const float *vtab, const float *a_g, const float *v_g,
+                                  const float *const *weights, int n_weights, int B, int cap, int A, int KN, int D,
+                                  int H, float *out, void *stream);
+int nsdp_decoder_fused_fwd_bf16_ragged(const float *xyz_q, const int32_t *offsets, const float *anchors, const int32_t *idx,
+                                       const float *qk, const float *vtab, const float *a_g, const float *v_g,
+                                       const void *const *weights, int n_weights, int B, int cap, int A, int KN, int D,
+                                       int H, float *out, void *stream);
 
 /* ----------------------------------------------------------------------------------------------
  * BatchNorm1d on channels-last rows x[R,C] (R = B*n, C % 4 == 0, C <= 1024), replacing the 35

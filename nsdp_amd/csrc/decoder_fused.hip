@@ -23,6 +23,7 @@
 #include <type_traits>
 #include "common.h"
 #include "prof.h"
+#include "ragged.h"
 
 namespace {
 
@@ -50,6 +51,9 @@ struct DecParams {
   const float *wout, *bout;     // [16,HP], [16]
   float *out;              // [B,NQ,3]
   int B, NQ, A, KN;
+  // packed (ragged) form, ragged.h: xyz_q [cap,3], idx [cap,KN], out [cap,3]; NQ unused
+  const int32_t *offsets;  // [B+1] device
+  int cap;
 };
 
 struct Vec {                    // one activation vector per row: NT tiles x 4 channels per lane
@@ -58,6 +62,10 @@ struct Vec {                    // one activation vector per row: NT tiles x 4 c
 
 constexpr int kWaves = 2;   // waves per workgroup: 2 x 39 KiB of private softmax state -> two workgroups per CU
 
+// Ragged = false: the rectangular [B,NQ] form, shape = blockIdx.y.  Ragged = true: a packed query set -- the wave's tile
+// index is mapped to (shape, first row, end row of the shape) from p.offsets on the device (ragged.h); everything
+// after that is the one body, so a row gets the same bits in either form.
+template <bool Ragged>
 __global__ __launch_bounds__(kWaves * 64) void decoder_fused_fwd_kernel(DecParams p) {
   // Architectural VGPRs stop at 256 per lane (the other 256 registers of the file are AGPRs, usable only
   // as MFMA operands), and the chain already keeps three 52-register activation vectors live.  The
@@ -67,13 +75,26 @@ __global__ __launch_bounds__(kWaves * 64) void decoder_fused_fwd_kernel(DecParam
   __shared__ float4 state[kWaves][3][DT][64];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int li = lane & 15, g = lane >> 4;
-  const int b = blockIdx.y;
-  const int q0 = (blockIdx.x * kWaves + wave) * 16;
-  if (q0 >= p.NQ) return;                          // no barriers in this kernel
-  int q = q0 + li;
-  const bool qvalid = q < p.NQ;
-  q = qvalid ? q : (p.NQ - 1);
-  const size_t qrow = static_cast<size_t>(b) * p.NQ + q;
+  int b;
+  size_t qrow;
+  bool qvalid;
+  if constexpr (Ragged) {
+    // (surplus tiles return; no barriers in this kernel.  b is wave-uniform by construction: scalar table bases)
+    int row0, end;
+    const int tile = __builtin_amdgcn_readfirstlane(static_cast<int>(blockIdx.x * kWaves + wave));
+    if (!nsdp::ragged_tile<16>(p.offsets, p.B, p.cap, tile, b, row0, end)) return;
+    const int q = row0 + li;                       // a shape's last tile is partial: lanes clamped to its last row, not stored
+    qvalid = q < end;
+    qrow = static_cast<size_t>(qvalid ? q : end - 1);
+  } else {
+    b = blockIdx.y;
+    const int q0 = (blockIdx.x * kWaves + wave) * 16;
+    if (q0 >= p.NQ) return;                        // no barriers in this kernel
+    int q = q0 + li;
+    qvalid = q < p.NQ;
+    q = qvalid ? q : (p.NQ - 1);
+    qrow = static_cast<size_t>(b) * p.NQ + q;
+  }
 
   const float qx = p.xyz_q[qrow * 3 + 0], qy = p.xyz_q[qrow * 3 + 1], qz = p.xyz_q[qrow * 3 + 2];
   const float *anch = p.anchors + static_cast<size_t>(b) * p.A * 3;
@@ -99,7 +120,8 @@ __global__ __launch_bounds__(kWaves * 64) void decoder_fused_fwd_kernel(DecParam
     asm volatile("" : "+s"(opaque0));
     const float *wd0 = p.wd0 + opaque0, *wd2 = p.wd2 + opaque0, *bd2 = p.bd2 + opaque0, *wg0 = p.wg0 + opaque0,
                 *bg0 = p.bg0 + opaque0, *wg2 = p.wg2 + opaque0, *bg2 = p.bg2 + opaque0;
-    const int a = p.idx[qrow * p.KN + slot];
+    int a = p.idx[qrow * p.KN + slot];
+    if constexpr (Ragged) a = min(max(a, 0), p.A - 1);   // (the packed form promises in-bounds accesses whatever its inputs hold)
     // relative coordinate, augmented with 1 for the bias column: lane group g carries component g
     const float rel = g == 0 ? qx - anch[a * 3 + 0]
                     : g == 1 ? qy - anch[a * 3 + 1]
@@ -168,18 +190,14 @@ __global__ __launch_bounds__(kWaves * 64) void decoder_fused_fwd_kernel(DecParam
   }
 }
 
-}  // namespace
-
-extern "C" int nsdp_decoder_fused_fwd(const float *xyz_q, const float *anchors, const int32_t *idx,
-                                      const float *qk, const float *vtab, const float *a_g, const float *v_g,
-                                      const float *const *weights, int n_weights, int B, int NQ, int A,
-                                      int KN, int D, int H, float *out, void *stream) {
-  if (static_cast<long long>(B) * NQ <= 0) return 0;
-  NSDP_REQUIRE(D == 200 && H == 128, "decoder_fused_fwd: built for dim=200, hidden_dim=128 (got %d, %d)", D, H);
-  NSDP_REQUIRE(n_weights == 17, "decoder_fused_fwd: expected 17 packed weight pointers, got %d", n_weights);
-  NSDP_REQUIRE(xyz_q && anchors && idx && qk && vtab && a_g && v_g && weights && out, "decoder_fused_fwd: null pointer");
-  NSDP_REQUIRE(B <= 65535, "decoder_fused_fwd: batch too large");
-  DecParams p;
+// host side of both entry points: argument checks and the parameter block (NQ / offsets, cap are the caller's to set)
+static int fill_params(const char *who, DecParams &p, const float *xyz_q, const float *anchors, const int32_t *idx,
+                       const float *qk, const float *vtab, const float *a_g, const float *v_g, const float *const *weights,
+                       int n_weights, int B, int A, int KN, int D, int H, float *out) {
+  NSDP_REQUIRE(D == 200 && H == 128, "%s: built for dim=200, hidden_dim=128 (got %d, %d)", who, D, H);
+  NSDP_REQUIRE(n_weights == 17, "%s: expected 17 packed weight pointers, got %d", who, n_weights);
+  NSDP_REQUIRE(xyz_q && anchors && idx && qk && vtab && a_g && v_g && weights && out, "%s: null pointer", who);
+  NSDP_REQUIRE(B <= 65535, "%s: batch too large", who);
   p.xyz_q = xyz_q; p.anchors = anchors; p.idx = idx; p.qk = qk; p.vtab = vtab; p.a_g = a_g; p.v_g = v_g;
   p.wd0 = weights[0];
   p.wd2 = weights[1]; p.bd2 = weights[2];
@@ -191,11 +209,45 @@ extern "C" int nsdp_decoder_fused_fwd(const float *xyz_q, const float *anchors, 
   p.w1 = weights[13]; p.b1 = weights[14];
   p.wout = weights[15]; p.bout = weights[16];
   p.out = out;
-  p.B = B; p.NQ = NQ; p.A = A; p.KN = KN;
+  p.B = B; p.NQ = 0; p.A = A; p.KN = KN;
+  p.offsets = nullptr; p.cap = 0;
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int nsdp_decoder_fused_fwd(const float *xyz_q, const float *anchors, const int32_t *idx,
+                                      const float *qk, const float *vtab, const float *a_g, const float *v_g,
+                                      const float *const *weights, int n_weights, int B, int NQ, int A,
+                                      int KN, int D, int H, float *out, void *stream) {
+  if (static_cast<long long>(B) * NQ <= 0) return 0;
+  DecParams p;
+  if (int rc = fill_params("decoder_fused_fwd", p, xyz_q, anchors, idx, qk, vtab, a_g, v_g, weights, n_weights, B, A, KN, D, H, out)) return rc;
+  p.NQ = NQ;
   hipStream_t st = nsdp::as_stream(stream);
   // algorithmic work: 2.484 MFLOP per query; bytes: coordinates, indices, output
   nsdp::prof::Scope scope(nsdp::prof::kDecoderFwd, st, 2.484e6 * static_cast<double>(B) * NQ,
                           static_cast<double>(B) * NQ * (24.0 + 4.0 * KN));
-  hipLaunchKernelGGL(decoder_fused_fwd_kernel, dim3(nsdp::ceil_div(NQ, 16 * kWaves), B), dim3(kWaves * 64), 0, st, p);
+  hipLaunchKernelGGL(decoder_fused_fwd_kernel<false>, dim3(nsdp::ceil_div(NQ, 16 * kWaves), B), dim3(kWaves * 64), 0, st, p);
   return nsdp::launch_status("decoder_fused_fwd_kernel");
+}
+
+extern "C" int nsdp_decoder_fused_fwd_ragged(const float *xyz_q, const int32_t *offsets, const float *anchors,
+                                             const int32_t *idx, const float *qk, const float *vtab, const float *a_g,
+                                             const float *v_g, const float *const *weights, int n_weights, int B,
+                                             int cap, int A, int KN, int D, int H, float *out, void *stream) {
+  if (static_cast<long long>(B) * cap <= 0) return 0;
+  DecParams p;
+  if (int rc = fill_params("decoder_fused_fwd_ragged", p, xyz_q, anchors, idx, qk, vtab, a_g, v_g, weights, n_weights, B, A, KN, D, H, out)) return rc;
+  NSDP_REQUIRE(offsets, "decoder_fused_fwd_ragged: null pointer (offsets)");
+  NSDP_REQUIRE(A >= 1, "decoder_fused_fwd_ragged: no anchors");
+  p.offsets = offsets; p.cap = cap;
+  hipStream_t st = nsdp::as_stream(stream);
+  // the host does not know how many of the cap rows are real (offsets live on the device and are not read back): the work
+  // and the bytes are accounted with cap, an UPPER bound -- rates derived from them are upper bounds too
+  nsdp::prof::Scope scope(nsdp::prof::kDecoderFwd, st, 2.484e6 * static_cast<double>(cap),
+                          static_cast<double>(cap) * (24.0 + 4.0 * KN));
+  const int tiles = static_cast<int>(nsdp::ragged_max_tiles(cap, B, 16));
+  hipLaunchKernelGGL(decoder_fused_fwd_kernel<true>, dim3(nsdp::ceil_div(tiles, kWaves)), dim3(kWaves * 64), 0, st, p);
+  return nsdp::launch_status("decoder_fused_fwd_kernel<ragged>");
 }

@@ -15,6 +15,7 @@
 
 #include "common.h"
 #include "prof.h"
+#include "ragged.h"
 
 #pragma clang fp contract(off)
 
@@ -24,20 +25,15 @@ constexpr int kTile = 1024;  // source points per LDS tile (16 KiB)
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
+// One lane's search: `tile` is the workgroup's LDS tile, `qp` the lane's query point (read when `active`), `source` the m
+// points of the lane's shape; the k best go to io[0..k) / dout[0..k) (dout may be NULL).  Every lane of the workgroup must
+// call it (barriers), with the same `source` and `m`.
 template <int K>
-__global__ __launch_bounds__(256) void knn_kernel(const float *__restrict__ query_all,
-                                                  const float *__restrict__ source_all, int n, int m,
-                                                  int k, int32_t *__restrict__ idx_all,
-                                                  float *__restrict__ dist_all) {
-  __shared__ float4 tile[kTile];
-  const int b = blockIdx.y;
-  const float *query = query_all + static_cast<size_t>(b) * n * 3;
-  const float *source = source_all + static_cast<size_t>(b) * m * 3;
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  const bool active = i < n;
+__device__ __forceinline__ void knn_scan(float4 *tile, const float *__restrict__ qp, const float *__restrict__ source, int m,
+                                         int k, bool active, int32_t *__restrict__ io, float *__restrict__ dout) {
   float qx = 0.f, qy = 0.f, qz = 0.f;
   if (active) {
-    qx = query[i * 3 + 0]; qy = query[i * 3 + 1]; qz = query[i * 3 + 2];
+    qx = qp[0]; qy = qp[1]; qz = qp[2];
   }
   float bd[K];
   int bi[K];
@@ -78,17 +74,46 @@ __global__ __launch_bounds__(256) void knn_kernel(const float *__restrict__ quer
     }
   }
   if (active) {
-    int32_t *io = idx_all + (static_cast<size_t>(b) * n + i) * k;
 #pragma unroll
     for (int t = 0; t < K; ++t)
       if (t < k) io[t] = bi[t];
-    if (dist_all) {
-      float *dout = dist_all + (static_cast<size_t>(b) * n + i) * k;
+    if (dout) {
 #pragma unroll
       for (int t = 0; t < K; ++t)
         if (t < k) dout[t] = bd[t];
     }
   }
+}
+
+template <int K>
+__global__ __launch_bounds__(256) void knn_kernel(const float *__restrict__ query_all,
+                                                  const float *__restrict__ source_all, int n, int m,
+                                                  int k, int32_t *__restrict__ idx_all,
+                                                  float *__restrict__ dist_all) {
+  __shared__ float4 tile[kTile];
+  const int b = blockIdx.y;
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  const size_t row = static_cast<size_t>(b) * n + i;
+  knn_scan<K>(tile, query_all + row * 3, source_all + static_cast<size_t>(b) * m * 3, m, k, i < n, idx_all + row * k,
+              dist_all ? dist_all + row * k : nullptr);
+}
+
+// The same search over a packed query set (ragged.h): query [cap,3], offsets [B+1] on the device, source [B,m,3].  A
+// workgroup's 256 queries belong to one shape -- its LDS tile holds that shape's source points -- and a shape's last
+// workgroup is partial.  Surplus workgroups return as a whole (before any barrier); rows at or beyond offsets[B] are not
+// written.
+template <int K>
+__global__ __launch_bounds__(256) void knn_ragged_kernel(const float *__restrict__ query, const int32_t *__restrict__ offsets,
+                                                         const float *__restrict__ source_all, int B, int cap, int m, int k,
+                                                         int32_t *__restrict__ idx_all, float *__restrict__ dist_all) {
+  __shared__ float4 tile[kTile];
+  int b, row0, end;
+  if (!nsdp::ragged_tile<256>(offsets, B, cap, static_cast<int>(blockIdx.x), b, row0, end)) return;
+  const int i = row0 + threadIdx.x;
+  const bool active = i < end;
+  const size_t row = static_cast<size_t>(active ? i : end - 1);         // (inactive lanes form no pointer past the buffers)
+  knn_scan<K>(tile, query + row * 3, source_all + static_cast<size_t>(b) * m * 3, m, k, active, idx_all + row * k,
+              dist_all ? dist_all + row * k : nullptr);
 }
 
 // Several lanes per query.  With one lane per query the kernel is one wave per SIMD at the encoder's sizes (2048
@@ -361,6 +386,15 @@ int launch(const float *q, const float *s, int B, int n, int m, int k, int32_t *
   return nsdp::launch_status("knn_kernel");
 }
 
+template <int K>
+int launch_ragged(const float *q, const int32_t *offsets, const float *s, int B, int cap, int m, int k, int32_t *idx,
+                  float *d2, hipStream_t st) {
+  NSDP_TRACE("knn_ragged<%d>", K);
+  const int tiles = static_cast<int>(nsdp::ragged_max_tiles(cap, B, 256));
+  hipLaunchKernelGGL((knn_ragged_kernel<K>), dim3(tiles), dim3(256), 0, st, q, offsets, s, B, cap, m, k, idx, d2);
+  return nsdp::launch_status("knn_ragged_kernel");
+}
+
 }  // namespace
 
 namespace nsdp {
@@ -381,4 +415,22 @@ extern "C" int nsdp_knn(const float *query, const float *source, int B, int n, i
   if (k <= 16) return launch<16>(query, source, B, n, m, k, idx_out, dist2_out, st);
   if (k <= 32) return launch<32>(query, source, B, n, m, k, idx_out, dist2_out, st);
   return launch<64>(query, source, B, n, m, k, idx_out, dist2_out, st);
+}
+
+extern "C" int nsdp_knn_ragged(const float *query, const int32_t *offsets, const float *source, int B, int cap, int m,
+                               int k, int32_t *idx_out, float *dist2_out, void *stream) {
+  if (static_cast<long long>(B) * cap <= 0 || k <= 0) return 0;
+  NSDP_REQUIRE(query && offsets && source && idx_out, "knn_ragged: null pointer");
+  NSDP_REQUIRE(k <= m, "knn_ragged: k=%d exceeds the number of source points m=%d", k, m);
+  NSDP_REQUIRE(k <= 64, "knn_ragged: k=%d > 64 is not supported", k);
+  NSDP_REQUIRE(B <= 65535, "knn_ragged: batch %d too large for one launch", B);
+  hipStream_t st = nsdp::as_stream(stream);
+  // the number of real rows is known to the device alone: bytes accounted with cap, an upper bound
+  nsdp::prof::Scope scope(nsdp::prof::kKnn, st, 0.0,
+                          12.0 * (static_cast<double>(cap) + static_cast<double>(B) * m) +
+                              4.0 * cap * k * (dist2_out ? 2 : 1));
+  if (k <= 8) return launch_ragged<8>(query, offsets, source, B, cap, m, k, idx_out, dist2_out, st);
+  if (k <= 16) return launch_ragged<16>(query, offsets, source, B, cap, m, k, idx_out, dist2_out, st);
+  if (k <= 32) return launch_ragged<32>(query, offsets, source, B, cap, m, k, idx_out, dist2_out, st);
+  return launch_ragged<64>(query, offsets, source, B, cap, m, k, idx_out, dist2_out, st);
 }

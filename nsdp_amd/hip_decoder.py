@@ -159,8 +159,9 @@ class _Pack:
         return self
 
 
-def decoder_forward(dec, xyz_q: torch.Tensor, encoding: dict) -> torch.Tensor:
-    """xyz_q [B,NQ,3] + encoding {z [B,C], anchors [B,A,3], anchor_feats [B,A,C]} -> [B,NQ,3]."""
+def _setup(dec, encoding):
+    """What both forms of the fused call share: the geometry check, the operand type, the weight pack of that type and the
+    encoding as the fp32 table kernels want it.  -> (bf16, pack, z, anchors, feats, context the tables are built in)."""
     if not supported(dec):
         raise _lib.NsdpHipError("fused decoder: built for dim=200, hidden_dim=128, n_blocks=5, out_dim=3")
     z, anchors, feats = encoding["z"], encoding["anchors"], encoding["anchor_feats"]
@@ -176,32 +177,94 @@ def decoder_forward(dec, xyz_q: torch.Tensor, encoding: dict) -> torch.Tensor:
     tables_f32 = precision.storage(torch.float32) if precision.is_bf16() else contextlib.nullcontext()
     if precision.is_bf16():
         z, feats = z.float(), feats.float()
+    return bf16, pack, z, anchors.contiguous().float(), feats, tables_f32
+
+
+def _shape_tables(pack, z, feats):
+    """The per-shape tables of the fused kernels (a few hundred rows, through the ordinary HIP linear): qk [B,A,DP], vtab
+    [B,A,DP], a_g [B,DP], v_g [B,DP]."""
+    tb = pack.tables
+    lin = lambda x, w, *a, **k: hip_linear.linear(x, w, *a, pack_owner=w, **k)      # (constant tables: packs cached on them)
+    q = lin(z, tb["w_qs"])                                                  # [B,DP] (pad channels = 0)
+    k_g = lin(z, tb["w_kg"])
+    v_g = lin(z, tb["w_vg"]).contiguous()
+    kf = lin(feats, tb["w_ks"])                                             # [B,A,DP]
+    vtab = lin(feats, tb["w_vs"]).contiguous()
+    qk = (q.unsqueeze(1) - kf).contiguous()
+    t = pack.tensors
+    h = lin(q - k_g, pack.gamma_rows[0], t[4], relu_out=True)               # global-token logits
+    a_g = lin(h, pack.gamma_rows[1], t[6]).contiguous()
+    return qk, vtab, a_g, v_g
+
+
+def decoder_forward(dec, xyz_q: torch.Tensor, encoding: dict) -> torch.Tensor:
+    """xyz_q [B,NQ,3] + encoding {z [B,C], anchors [B,A,3], anchor_feats [B,A,C]} -> [B,NQ,3]."""
+    bf16, pack, z, anchors, feats, tables_f32 = _setup(dec, encoding)
     ct = dec.ct1
     B, NQ, _ = xyz_q.shape
     A = anchors.shape[1]
     xyz_q_in = xyz_q
     xyz_q = xyz_q.contiguous().float()
-    anchors = anchors.contiguous().float()
     with torch.no_grad(), _lib.on_device(xyz_q), tables_f32:
         idx = encoding.get("query_idx") if encoding.get("query_points") is xyz_q_in else None      # (searched ahead: Deformation_Networks.geometry)
         if idx is None:
             idx = pointnet2_utils.knn(xyz_q, anchors, ct.nneigh)                # [B,NQ,k] int32
-        tb = pack.tables
-        lin = lambda x, w, *a, **k: hip_linear.linear(x, w, *a, pack_owner=w, **k)      # (constant tables: packs cached on them)
-        q = lin(z, tb["w_qs"])                                                  # [B,DP] (pad channels = 0)
-        k_g = lin(z, tb["w_kg"])
-        v_g = lin(z, tb["w_vg"]).contiguous()
-        kf = lin(feats, tb["w_ks"])                                             # [B,A,DP]
-        vtab = lin(feats, tb["w_vs"]).contiguous()
-        qk = (q.unsqueeze(1) - kf).contiguous()
-        t = pack.tensors
-        h = lin(q - k_g, pack.gamma_rows[0], t[4], relu_out=True)               # global-token logits
-        a_g = lin(h, pack.gamma_rows[1], t[6]).contiguous()
+        qk, vtab, a_g, v_g = _shape_tables(pack, z, feats)
         out = torch.empty(B, NQ, OUT, dtype=torch.float32, device=xyz_q.device)
         name = "nsdp_decoder_fused_fwd_bf16" if bf16 else "nsdp_decoder_fused_fwd"
         _lib.check(getattr(_lib.lib(), name)(
             _lib.fptr(xyz_q, "xyz_q"), _lib.fptr(anchors, "anchors"), _lib.iptr(idx, "idx"),
             _lib.fptr(qk, "qk"), _lib.fptr(vtab, "vtab"), _lib.fptr(a_g, "a_g"), _lib.fptr(v_g, "v_g"),
-            pack.ptrs, len(t), B, NQ, A, ct.nneigh, DIM, HIDDEN, _lib.fptr(out, "out"), _lib.stream_ptr()),
+            pack.ptrs, len(pack.tensors), B, NQ, A, ct.nneigh, DIM, HIDDEN, _lib.fptr(out, "out"), _lib.stream_ptr()),
             name)
     return out
+
+
+def ragged_refusal(dec):
+    """Why a packed query set cannot be decoded right now (None: it can).  The packed form exists as the fused kernels alone
+    -- there is no layered path to fall to -- so every condition under which the rectangular call would take the layers is a
+    refusal here."""
+    if torch.is_grad_enabled():
+        return ("autograd is enabled: a packed (ragged) query set is decoded by the fused inference kernels only, which have "
+                "no backward -- call under torch.no_grad()")
+    if not ENABLED:
+        return "the fused decoder is switched off (NSDP_FUSED_DECODER=0 / hip_decoder.ENABLED = False) and the layered decoder has no ragged form"
+    if MODE != "bf16" and precision.is_bf16():
+        return ("bf16 storage with the fp32 fused kernel (hip_decoder.MODE = 'f32'): the rectangular call runs the layered bf16 "
+                "decoder there, which has no ragged form -- select the bf16-operand kernel (NSDP_FUSED_DECODER_DTYPE=bf16)")
+    if not supported(dec):
+        return "decoder geometry: the fused kernels are built for dim=200, hidden_dim=128, n_blocks=5, out_dim=3"
+    return None
+
+
+def decoder_forward_ragged(dec, points, encoding: dict, out=None):
+    """``decoder_forward`` for a packed query set: points = RaggedPoints (packed [cap,3], offsets [B+1] on the device) + the
+    encoding of B shapes -> RaggedPoints over [cap,3] (rows at or beyond offsets[B] are not written; ``out``: a [cap,3] buffer
+    of the caller's).  One kNN launch and one fused launch whose grids follow cap and B alone -- nothing here reads the
+    offsets on the host, so the call can be captured once and replayed for any mix of sizes.  No layered fallback."""
+    why = ragged_refusal(dec)
+    if why is not None:
+        raise _lib.NsdpHipError("ragged decode refused: " + why)
+    bf16, pack, z, anchors, feats, tables_f32 = _setup(dec, encoding)
+    ct = dec.ct1
+    xyz_q = points.packed.contiguous().float()
+    cap, (B, A) = xyz_q.shape[0], anchors.shape[:2]
+    if xyz_q.dim() != 2 or xyz_q.shape[1] != 3:
+        raise _lib.NsdpHipError(f"ragged decode: packed points must be [cap, 3], got {tuple(xyz_q.shape)}")
+    if points.batch != B:
+        raise _lib.NsdpHipError(f"ragged decode: {points.batch} shapes of points against an encoding of {B}")
+    with torch.no_grad(), _lib.on_device(xyz_q), tables_f32:
+        if out is None:
+            out = torch.empty(cap, OUT, dtype=torch.float32, device=xyz_q.device)
+        elif tuple(out.shape) != (cap, OUT):
+            raise _lib.NsdpHipError(f"ragged decode: out must be [{cap}, {OUT}], got {tuple(out.shape)}")
+        if cap:
+            idx = pointnet2_utils.knn_ragged(xyz_q, points.offsets, anchors, ct.nneigh)      # [cap,k] int32
+            qk, vtab, a_g, v_g = _shape_tables(pack, z, feats)
+            name = "nsdp_decoder_fused_fwd_bf16_ragged" if bf16 else "nsdp_decoder_fused_fwd_ragged"
+            _lib.check(getattr(_lib.lib(), name)(
+                _lib.fptr(xyz_q, "xyz_q"), _lib.iptr(points.offsets, "offsets"), _lib.fptr(anchors, "anchors"), _lib.iptr(idx, "idx"),
+                _lib.fptr(qk, "qk"), _lib.fptr(vtab, "vtab"), _lib.fptr(a_g, "a_g"), _lib.fptr(v_g, "v_g"),
+                pack.ptrs, len(pack.tensors), B, cap, A, ct.nneigh, DIM, HIDDEN, _lib.fptr(out, "out"), _lib.stream_ptr()),
+                name)
+    return points.like(out)

@@ -17,6 +17,17 @@ ran eagerly, and ``ranks_agree`` (every rank's gathered predictions have the sam
 predictions as DIR/<key>.npy.  ``--decoder-dtype bf16`` selects the fused decoder's bf16-operand kernel on every rank
 (hip_decoder.MODE; ``decoder_dtype`` in the line); one extra call with the fp32 kernel after the timed region then gives
 ``max_abs_diff_vs_f32`` and ``l2_vs_f32`` (max over shapes of the RMS point distance) of the mesh-vertex predictions.
+
+    python -m nsdp_amd.infer CONFIG --vertex-counts n1,n2,... [--capacity C] [--graph] [--decoder-dtype f32|bf16] ...
+
+Meshes of DIFFERENT vertex counts in one call (nsdp_amd.ragged; one GPU): B = the number of counts, shape b decodes the first
+n_b of the max(counts) synthetic vertices -- the rows the rectangular call at ``--batch B --queries max(counts)`` decodes for
+it.  The step is ``ragged.RaggedTestOnBatch`` (capacity C, default the total; ``--graph``: captured once, replayed).  The line
+gains ``ragged``, ``vertex_counts``, ``total``, ``capacity`` and, measured after the timed region in the same process in
+interleaved repetitions (median; every repetition in ``*_reps``): ``ms_ragged`` (the same step again), ``ms_padded`` (the
+rectangular call at B x max(counts), replayed under ``--graph``), ``ms_per_shape_loop`` (B eager calls at batch 1, the only
+exact alternative without the packed form) and ``equal_to_padded`` (every shape's rows bit-equal to the padded call's).
+``--out DIR``: verts_tgt_pred.npy is the packed [total, 3] array, verts_offsets.npy the [B + 1] offsets.
 """
 from __future__ import annotations
 
@@ -61,15 +72,111 @@ def build_parser():
                     help="capture each rank's encode and local decode once and replay it; the gather runs eagerly after the replay")
     ap.add_argument("--weight_file", default=None, help="weights of the whole model (default: procedural weights)")
     ap.add_argument("--out", default=None, help="directory for rank 0's predictions (<key>.npy)")
+    ap.add_argument("--vertex-counts", default=None,
+                    help="comma-separated vertex counts, one per shape: decode the meshes as one packed (ragged) set")
+    ap.add_argument("--capacity", type=int, default=None,
+                    help="rows of the packed vertex buffer (default: the sum of --vertex-counts); a captured graph serves every "
+                         "batch of as many shapes whose vertices sum to at most this")
+    ap.add_argument("--reps", type=int, default=5, help="--vertex-counts: interleaved repetitions of the comparison timings")
     ap.add_argument("--decoder-dtype", default=None, choices=["f32", "bf16"],
                     help="operand type of the fused decoder kernel on every rank (default: NSDP_FUSED_DECODER_DTYPE, else f32)")
     return ap
+
+
+def _ragged(args, config, model, test_fn, dd, counts, ns):
+    """The --vertex-counts run (one GPU): timed packed step, then the comparison timings and the bit comparison."""
+    import statistics
+    import numpy as np
+    import torch
+    from . import hip_decoder
+    from .query_shard import QueryShards, query_sharded
+    from .ragged import RaggedPoints, RaggedTestOnBatch
+    B, total = len(counts), sum(counts)
+    capacity = args.capacity or total
+    verts = RaggedPoints.from_list([dd["verts_src"][b, :n] for b, n in enumerate(counts)])
+    rdd = {k: v for k, v in dd.items() if k not in ("verts_src", "verts_tgt")}
+    rdd["verts_src"] = verts
+    step = RaggedTestOnBatch(test_fn, capacity, graph=args.graph)
+    padded = query_sharded(test_fn, QueryShards(0, 1), graph=args.graph)
+    per_shape = [{"surface_samples_inputs": dd["surface_samples_inputs"][b:b + 1].contiguous(),
+                  "surface_samples_src": dd["surface_samples_src"][b:b + 1].contiguous(),
+                  "verts_src": dd["verts_src"][b:b + 1, :n].contiguous()} for b, n in enumerate(counts)]
+
+    def run_ragged():
+        step(model, rdd, config)
+
+    def run_padded():
+        padded(model, dd, config)
+
+    def run_loop():
+        for one in per_shape:
+            test_fn(model, dict(one), config)
+
+    def timed(fn, n):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        for _ in range(n):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / max(1, n)
+
+    for _ in range(max(args.warmup, 1 if args.graph else 0)):      # (--graph: the first call captures)
+        run_ragged()
+    ms = timed(run_ragged, args.steps)
+    replays, eager_calls = step.replays, step.eager_calls
+    pred = {k: (rdd[k].packed if k == "verts_tgt_pred" else rdd[k]).clone() for k in KEYS}
+    # the comparisons: after the timed region, same process, interleaved repetitions
+    run_padded()
+    run_loop()
+    want = dd["verts_tgt_pred"]
+    got = rdd["verts_tgt_pred"].split()
+    equal = all(torch.equal(got[b], want[b, :n]) for b, n in enumerate(counts)) and \
+        torch.equal(rdd["surface_samples_tgt_pred"], dd["surface_samples_tgt_pred"])
+    reps = {"ms_ragged": [], "ms_padded": [], "ms_per_shape_loop": []}
+    for _ in range(max(1, args.reps)):
+        reps["ms_ragged"].append(timed(run_ragged, args.steps))
+        reps["ms_padded"].append(timed(run_padded, args.steps))
+        reps["ms_per_shape_loop"].append(timed(run_loop, args.steps))
+    if args.out:
+        os.makedirs(args.out, exist_ok=True)
+        for k in KEYS:
+            np.save(os.path.join(args.out, k + ".npy"), pred[k].cpu().numpy())
+        np.save(os.path.join(args.out, "verts_offsets.npy"), verts.offsets.cpu().numpy())
+    line = {"metric": "dense_inference_ragged", "model_type": config["model"]["type"], "world": 1, "graph": bool(args.graph),
+            "ragged": True, "vertex_counts": counts, "total": total, "capacity": capacity, "batch": B, "surface": ns,
+            "queries_padded": B * max(counts), "steps": args.steps, "warmup": args.warmup, "reps": max(1, args.reps),
+            "decoder_dtype": hip_decoder.MODE, "ms_per_call": round(ms, 4),
+            "query_points_per_s": round(total / (ms / 1e3), 1) if ms > 0 else None,
+            "replays": replays, "eager_calls": eager_calls, "padded_replays": padded.replays,
+            **{k: round(statistics.median(v), 4) for k, v in reps.items()},
+            **{k + "_reps": [round(x, 4) for x in v] for k, v in reps.items()},
+            "equal_to_padded": bool(equal)}
+    print(json.dumps(line), flush=True)
+    step.close()
+    padded.close()
+    return 0
 
 
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     ap = build_parser()
     args = ap.parse_args(argv)
+    counts = None
+    if args.vertex_counts is not None:
+        try:
+            counts = [int(c) for c in args.vertex_counts.split(",") if c.strip() != ""]
+        except ValueError:
+            counts = []
+        if not counts or min(counts) < 0 or max(counts) == 0:
+            sys.exit(f"nsdp_amd.infer: --vertex-counts wants non-negative integers n1,n2,... (not all zero), got {args.vertex_counts!r}")
+        if args.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            sys.exit("nsdp_amd.infer: --vertex-counts runs on one GPU (splitting a ragged set over ranks is not implemented)")
+        if args.capacity is not None and args.capacity < sum(counts):
+            sys.exit(f"nsdp_amd.infer: --capacity {args.capacity} is below the {sum(counts)} vertices of --vertex-counts")
+        if args.batch is not None and args.batch != len(counts):
+            sys.exit(f"nsdp_amd.infer: --batch {args.batch} against {len(counts)} vertex counts")
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         from .train import launch_ranks
@@ -107,10 +214,10 @@ def main(argv=None):
     from .model import build_model
     from .query_shard import QueryShards, query_sharded
     config = load_config(args.config_file)
-    batch = args.batch or int(config.get("test", {}).get("batch_size", 1) or 1)
+    batch = len(counts) if counts else (args.batch or int(config.get("test", {}).get("batch_size", 1) or 1))
     ns = args.surface or int(config.get("data", {}).get("num_surf_samples", 0) or
                              config["model"]["encoder_kwargs"]["npoints_per_layer"][0])
-    nq = int(args.queries)
+    nq = max(counts) if counts else int(args.queries)
     _pyramid(config, ns)
     model, _, _, test_fn = build_model(config, weight_file=args.weight_file, device="cpu")
     if args.weight_file is None:
@@ -122,6 +229,8 @@ def main(argv=None):
     dd["surface_samples_src"] = dd["surface_samples_inputs"][:, :, 0:3].contiguous()
     dd["verts_src"], dd["verts_tgt"] = dd.pop("space_samples_src"), dd.pop("space_samples_tgt")
 
+    if counts:
+        return _ragged(args, config, model, test_fn, dd, counts, ns)
     shards = QueryShards(rank, world)
     step = query_sharded(test_fn, shards, graph=args.graph)
 

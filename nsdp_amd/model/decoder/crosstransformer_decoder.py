@@ -6,6 +6,7 @@ import torch.nn as nn
 
 from .. import ops
 from ... import hip_decoder, hip_linear, precision
+from ...ragged import RaggedPoints
 from .blocks import CrossTransformerBlock, ResnetBlockFC
 
 # bf16 storage: the decoder's residual trunk in fp32 storage (NSDP_BF16_TRUNK=f32), see forward()
@@ -14,7 +15,8 @@ TRUNK_F32 = __import__("os").environ.get("NSDP_BF16_TRUNK", "bf16") == "f32"
 
 class CrossTransformerDecoder(nn.Module):
     """xyz_q [B,NQ,3] + encoding -> [B,NQ,out_dim]
-    (reference model/decoder/crosstransformer_decoder.py:24-70)."""
+    (reference model/decoder/crosstransformer_decoder.py:24-70).  xyz_q a RaggedPoints (nsdp_amd.ragged: meshes of different
+    sizes, packed) -> a RaggedPoints; inference only, by the fused kernels only."""
 
     def __init__(self, dim_inp, dim, nneigh=7, hidden_dim=64, n_blocks=5, out_dim=1):
         super().__init__()
@@ -29,6 +31,8 @@ class CrossTransformerDecoder(nn.Module):
     def prefetch(self, xyz_q, anchors, after=None):
         """CrossTransformerBlock.prefetch for this decoder's attention block (None where forward() would not use it: the
         no-grad path runs the fused whole-decoder kernel)."""
+        if isinstance(xyz_q, RaggedPoints):
+            return None
         if hip_decoder.fused_for_inference() and not torch.is_grad_enabled() and hip_decoder.supported(self):
             return None
         return self.ct1.prefetch(xyz_q, anchors, after)
@@ -45,6 +49,10 @@ class CrossTransformerDecoder(nn.Module):
         return {"query_idx": ops.knn_indices(xyz_q, anchors, self.ct1.nneigh)}
 
     def forward(self, xyz_q, encoding):
+        if isinstance(xyz_q, RaggedPoints):
+            # the dispatch condition of the fused call below; where that one would fall to the layers this one raises
+            # (hip_decoder.ragged_refusal names the reason)
+            return hip_decoder.decoder_forward_ragged(self, xyz_q, encoding)
         if hip_decoder.fused_for_inference() and not torch.is_grad_enabled() and hip_decoder.supported(self):
             # inference: kNN + one fused kernel (18 dense layers + softmax in registers), nsdp_decoder_fused_fwd; with
             # hip_decoder.MODE == "bf16" its bf16-operand form, in either storage mode

@@ -11,6 +11,8 @@ import torch.nn as nn
 from .decoder import decoder_dict
 from .encoder import encoder_dict
 from .utils import compute_l2_error
+from .. import ragged
+from ..ragged import RaggedPoints
 
 # One encoder pass per distinct surface cloud (NSDP_ENCODE_ONCE=0: one per module call, the reference's op sequence -- A/B)
 ENCODE_ONCE = os.environ.get("NSDP_ENCODE_ONCE", "1") != "0"
@@ -64,16 +66,18 @@ class Deformation_Networks(nn.Module):
             enc = self.encoder(x, geometry=geometry["encoder"])
             enc["query_idx"], enc["query_points"] = geometry["query_idx"], geometry["query_points"]
             return enc
-        if (DECODER_PREFETCH and queries is not None and queries.is_cuda and hasattr(self.decoder, "prefetch")
+        if (DECODER_PREFETCH and torch.is_tensor(queries) and queries.is_cuda and hasattr(self.decoder, "prefetch")
                 and "on_anchors" in inspect.signature(self.encoder.forward).parameters):
             return self.encoder(x, on_anchors=lambda anchors, after: self.decoder.prefetch(queries, anchors, after))
         return self.encoder(x)
 
     def decode(self, points, encoding):
+        """points [B,NQ,3] -> [B,NQ,3]; a RaggedPoints (meshes of different sizes, nsdp_amd.ragged) -> a RaggedPoints."""
         return self.decoder(points, encoding)
 
     def forward(self, points, surface_samples_inputs, geometry=None):
-        points = points if points.is_contiguous() else points.contiguous()
+        if not isinstance(points, RaggedPoints):
+            points = points if points.is_contiguous() else points.contiguous()
         return self.decoder(points, self.encode(surface_samples_inputs, queries=points, geometry=geometry))
 
 
@@ -113,9 +117,18 @@ def validate_on_batch_with_cano(model, data_dict, config):
     return compute_l2_error(pred, data_dict["space_samples_tgt"]).item()
 
 
+def l2_error_of(pred, target):
+    """compute_l2_error of a dense-inference step; for a packed vertex set (RaggedPoints) the mean over the shapes of the
+    per-shape error, on the device (ragged.l2_error)."""
+    if isinstance(pred, RaggedPoints):
+        return ragged.l2_error(pred, ragged.as_ragged(target))
+    return compute_l2_error(pred, target)
+
+
 @torch.no_grad()
 def test_on_batch_with_cano(model, data_dict, config, compute_loss=False):
-    """Dense inference: surface samples, then all mesh vertices (reference :90-109)."""
+    """Dense inference: surface samples, then all mesh vertices (reference :90-109).  ``data_dict["verts_src"]`` may be a
+    RaggedPoints (meshes of different vertex counts, packed): ``verts_tgt_pred`` is then one too."""
     inputs = data_dict["surface_samples_inputs"]
     if ENCODE_ONCE:
         # the reference runs the module twice on the same surface input (:96, :101): same encoding both times
@@ -127,7 +140,7 @@ def test_on_batch_with_cano(model, data_dict, config, compute_loss=False):
         deformed_verts = model(data_dict["verts_src"], inputs)
     data_dict["verts_tgt_pred"] = deformed_verts
     if compute_loss:
-        loss = compute_l2_error(deformed_verts, data_dict["verts_tgt"])
+        loss = l2_error_of(deformed_verts, data_dict["verts_tgt"])
     else:
         loss = torch.zeros((1), dtype=torch.float32)
     return loss.item(), data_dict

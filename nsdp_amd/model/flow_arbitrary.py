@@ -10,6 +10,7 @@ import torch.nn as nn
 from .. import hip_batchnorm, hip_decoder, precision
 from . import deformation_networks
 from .utils import compute_l2_error
+from ..ragged import RaggedPoints
 
 
 class FlowArbitrary(nn.Module):
@@ -38,21 +39,30 @@ class FlowArbitrary(nn.Module):
         with self._canonicalize_storage(), hip_decoder.canonicalize_mode():
             if not deformation_networks.ENCODE_ONCE:
                 return [net(q, surface_samples_src) for q in query_sets]
+            if any(isinstance(q, RaggedPoints) for q in query_sets):
+                # a packed vertex set beside the (rectangular) surface: one encoding, one decode per set
+                with hip_batchnorm.running_updates(len(query_sets)):
+                    encoding = net.encode(surface_samples_src)
+                return [self._decode_canonical(net, q if isinstance(q, RaggedPoints) else q.contiguous(), encoding)
+                        for q in query_sets]
             queries = query_sets[0] if len(query_sets) == 1 else torch.cat(list(query_sets), dim=1)
             queries = queries if queries.is_contiguous() else queries.contiguous()
             with hip_batchnorm.running_updates(len(query_sets)):      # (inert on eval-mode norms)
                 encoding = net.encode(surface_samples_src, queries=queries)
-            if precision.is_bf16() and precision.canonicalize_decoder_f32():
-                # the middle point of the mixed storage (precision.py): bf16 encoder, fp32 decoder -- the encoding (one latent
-                # code and 100 anchor features per shape) is cast once, the per-point chain runs in fp32 storage
-                with precision.storage(torch.float32):
-                    enc32 = {k: (v.float() if torch.is_tensor(v) and v.dtype is torch.bfloat16 else v) for k, v in encoding.items()}
-                    out = net.decode(queries, enc32)
-            else:
-                out = net.decode(queries, encoding)
+            out = self._decode_canonical(net, queries, encoding)
             if len(query_sets) == 1:
                 return [out]
             return list(torch.split(out, [q.shape[1] for q in query_sets], dim=1))
+
+    @staticmethod
+    def _decode_canonical(net, queries, encoding):
+        if precision.is_bf16() and precision.canonicalize_decoder_f32():
+            # the middle point of the mixed storage (precision.py): bf16 encoder, fp32 decoder -- the encoding (one latent
+            # code and 100 anchor features per shape) is cast once, the per-point chain runs in fp32 storage
+            with precision.storage(torch.float32):
+                enc32 = {k: (v.float() if torch.is_tensor(v) and v.dtype is torch.bfloat16 else v) for k, v in encoding.items()}
+                return net.decode(queries, enc32)
+        return net.decode(queries, encoding)
 
     def deform_input(self, surf_src2cano, surface_samples_tgt, cano_handle_sample_mask):
         return torch.cat([surf_src2cano, surface_samples_tgt, cano_handle_sample_mask], dim=-1).contiguous()
@@ -60,7 +70,7 @@ class FlowArbitrary(nn.Module):
     def forward(self, space_samples_src, surface_samples_src, surface_samples_tgt, cano_handle_sample_mask):
         space_src2cano, surf_src2cano = self.canonicalize([space_samples_src, surface_samples_src], surface_samples_src)
         deform_in = self.deform_input(surf_src2cano, surface_samples_tgt, cano_handle_sample_mask)
-        return self.model_deform(space_src2cano.contiguous(), deform_in)
+        return self.model_deform(space_src2cano if isinstance(space_src2cano, RaggedPoints) else space_src2cano.contiguous(), deform_in)
 
 
 def _split(data_dict):
@@ -103,7 +113,8 @@ def validate_on_batch_with_arbitrary(model, data_dict, config):
 
 @torch.no_grad()
 def test_on_batch_with_arbitrary(model, data_dict, config, compute_loss=False):
-    """reference model/flow_arbitrary.py:65-85."""
+    """reference model/flow_arbitrary.py:65-85.  ``data_dict["verts_src"]`` may be a RaggedPoints (meshes of different vertex
+    counts, packed): both networks decode it ragged and ``verts_tgt_pred`` is one."""
     src, tgt, mask = _split(data_dict)
     if deformation_networks.ENCODE_ONCE:
         # the reference's two model() calls (:71, :76) run six encoder passes over two distinct clouds: the source cloud
@@ -111,13 +122,14 @@ def test_on_batch_with_arbitrary(model, data_dict, config, compute_loss=False):
         surf2cano, verts2cano = model.canonicalize([src, data_dict["verts_src"]], src)
         encoding = model.model_deform.encode(model.deform_input(surf2cano, tgt, mask))
         data_dict["surface_samples_tgt_pred"] = model.model_deform.decode(surf2cano.contiguous(), encoding)
-        deformed_verts = model.model_deform.decode(verts2cano.contiguous(), encoding)
+        deformed_verts = model.model_deform.decode(
+            verts2cano if isinstance(verts2cano, RaggedPoints) else verts2cano.contiguous(), encoding)
     else:
         data_dict["surface_samples_tgt_pred"] = model(src, src, tgt, mask)
         deformed_verts = model(data_dict["verts_src"], src, tgt, mask)
     data_dict["verts_tgt_pred"] = deformed_verts
     if compute_loss:
-        loss = compute_l2_error(deformed_verts, data_dict["verts_tgt"])
+        loss = deformation_networks.l2_error_of(deformed_verts, data_dict["verts_tgt"])
     else:
         loss = torch.zeros((1), dtype=torch.float32)
     return loss.item(), data_dict

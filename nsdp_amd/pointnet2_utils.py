@@ -53,6 +53,29 @@ def knn(query: torch.Tensor, source: torch.Tensor, k: int, return_dist: bool = F
     return (idx, d2) if return_dist else idx
 
 
+def knn_ragged(query: torch.Tensor, offsets: torch.Tensor, source: torch.Tensor, k: int, return_dist: bool = False,
+               idx_out=None, dist_out=None):
+    """``knn`` over a packed query set (nsdp_amd.ragged): query (cap,3), offsets (B+1) int32 on the device, source (B,m,3) ->
+    idx (cap,k) int32 (and dist2 (cap,k)); row r of shape b is searched in source[b].  Rows at or beyond offsets[B] are not
+    written (``idx_out`` / ``dist_out``: buffers of the caller's, e.g. the static ones of a captured graph).  The host never
+    reads ``offsets``.  One lane per query (the decoder's case: few source points); the bits of ``knn`` on each shape alone."""
+    with on_device(query):
+        if query.dim() != 2 or query.shape[1] != 3 or source.dim() != 3 or source.shape[2] != 3:
+            raise _lib.NsdpHipError(f"knn_ragged: query (cap,3) and source (B,m,3), got {tuple(query.shape)}, {tuple(source.shape)}")
+        cap, (B, m) = query.shape[0], source.shape[:2]
+        if offsets.numel() != B + 1:
+            raise _lib.NsdpHipError(f"knn_ragged: {B} shapes need {B + 1} offsets, got {offsets.numel()}")
+        idx = torch.empty((cap, int(k)), dtype=torch.int32, device=query.device) if idx_out is None else idx_out
+        d2 = dist_out if dist_out is not None else (
+            torch.empty((cap, int(k)), dtype=torch.float32, device=query.device) if return_dist else None)
+        if tuple(idx.shape) != (cap, int(k)) or (d2 is not None and tuple(d2.shape) != (cap, int(k))):
+            raise _lib.NsdpHipError(f"knn_ragged: output buffers must be ({cap},{int(k)})")
+        check(lib().nsdp_knn_ragged(fptr(query, "query"), iptr(offsets, "offsets"), fptr(source, "source"), _c_int(B),
+                                    _c_int(cap), _c_int(m), _c_int(int(k)), iptr(idx, "idx_out"),
+                                    optptr(None) if d2 is None else fptr(d2, "dist_out"), stream_ptr()), "nsdp_knn_ragged")
+    return (idx, d2) if (return_dist or dist_out is not None) else idx
+
+
 def gather_rows(points: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
     """index_points for a 2-D index: points (B,N,C), idx (B,S) int32 -> (B,S,C)."""
     B, N, C = points.shape

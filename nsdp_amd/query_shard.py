@@ -154,6 +154,13 @@ def _local_form(test_on_batch):
     return forms[test_on_batch]
 
 
+def _refuse_ragged(data_dict):
+    from .ragged import RaggedPoints
+    if isinstance(data_dict.get("verts_src"), RaggedPoints):
+        raise NotImplementedError("query_sharded: splitting a ragged (packed) vertex set over ranks is not implemented -- "
+                                  "decode it on one GPU (ragged.RaggedTestOnBatch) or pad the batch to a [B, max, 3] tensor")
+
+
 class QueryShardedTestOnBatch:
     """``fn(model, data_dict, config, compute_loss=False) -> (loss, data_dict)`` with the query points split over the ranks
     (see ``query_sharded``).  ``graph=True``: the first call captures this rank's encode and local decode
@@ -172,6 +179,7 @@ class QueryShardedTestOnBatch:
     def local(self, model, data_dict):
         """This rank's predictions, {key: (rows, total rows)}: enqueued on the current stream, nothing gathered."""
         require_supported()
+        _refuse_ragged(data_dict)
         with torch.no_grad():
             return self.local_fn(model, data_dict, self.shards)
 
@@ -201,6 +209,7 @@ class QueryShardedTestOnBatch:
     @torch.no_grad()
     def __call__(self, model, data_dict, config, compute_loss=False):
         from .model.utils import compute_l2_error
+        _refuse_ragged(data_dict)
         if self.graph:
             local = self._replayed(model, data_dict)
         else:
