@@ -132,6 +132,34 @@ int nsdp_knn(const float *query, const float *source, int B, int n, int m, int k
 int nsdp_knn_ragged(const float *query, const int32_t *offsets, const float *source, int B, int cap, int m, int k,
                     int32_t *idx_out, float *dist2_out, void *stream);
 
+/* Packed SOURCE sets (ABI version 10): a batch of surface clouds of different sample counts, xyz(cap,3) + offsets(B+1) in the
+ * layout above.  Besides `cap` and `B` the host passes `n_max`, an upper bound of any shape's row count: it sizes workgroups, LDS
+ * and scratch.  The kernels clamp the offsets as above and a shape's row count to n_max on top -- a corrupt offsets tensor or a
+ * too-small n_max gives wrong numbers, never an access outside the buffers.  Both entry points emit PACKED-ROW indices
+ * (offsets[b] + local index), so the gather / relative-coordinate / attention kernels run on the packed rows viewed as one
+ * shape (1,cap,.).
+ *
+ * Farthest-point sampling, one workgroup per shape: idx_out(B,nsamples); shape b samples its own n_b = offsets[b+1] -
+ * offsets[b] rows with its own tie-rule block size min(512, 2^floor(log2 n_b)), derived on the device.  idx_out[b] - offsets[b]
+ * equals nsdp_furthest_point_sampling on that shape alone (B = 1, N = n_b), ties included, whatever n_max is: the arg-max key
+ * is a maximum over all points, independent of the thread partition.  n_max picks the kernel form (registers up to 8192 rows;
+ * beyond that the running distances live in `tmp`, (cap) f32, which may be NULL otherwise).  A shape without rows gets
+ * offsets[b] in every slot (clamped into [0, cap)). */
+int nsdp_furthest_point_sampling_ragged(const float *xyz_packed, const int32_t *offsets, int B, int cap, int n_max,
+                                        int nsamples, float *tmp, int32_t *idx_out, void *stream);
+
+/* nsdp_knn against a packed source set source(cap,3) / offsets(B+1), in two forms.
+ *   query_offsets == NULL: rectangular queries query(B,n,3) -> idx(B,n,k), dist2_out(B,n,k) or NULL; shape b's queries search
+ *     shape b's rows.
+ *   query_offsets != NULL: packed queries query(qcap,3) / query_offsets(B+1) -> idx(qcap,k), dist2_out(qcap,k) or NULL (`n` is
+ *     ignored); a workgroup's 256 queries belong to one shape, rows at or beyond query_offsets[B] are not written.  The
+ *     self-search passes the source set as the query set as well.
+ * Order ascending (distance, index) with nsdp_knn's arithmetic: per shape, idx - offsets[b] and the distance bits equal
+ * nsdp_knn on that shape alone.  k <= 64; a shape with fewer than k rows (a corrupt offsets tensor: the host validates) fills
+ * the surplus slots with its first row's index (clamped into [0, cap)) and FLT_MAX. */
+int nsdp_knn_ragged_source(const float *query, const int32_t *query_offsets, const float *source, const int32_t *offsets, int B,
+                           int n, int qcap, int cap, int n_max, int k, int32_t *idx_out, float *dist2_out, void *stream);
+
 /* index_points(points(B,N,C), idx(B,S)) -> (B,S,C) (row gather; model/utils.py:58-70) */
 int nsdp_gather_rows(const float *points, const int32_t *idx, int B, int N, int C, int S, float *out,
                      void *stream);

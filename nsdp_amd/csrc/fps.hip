@@ -21,6 +21,7 @@
 
 #include "common.h"
 #include "prof.h"
+#include "ragged.h"
 
 #pragma clang fp contract(off)
 
@@ -82,18 +83,14 @@ __device__ __forceinline__ bool point_valid(float x, float y, float z) {
   return !(static_cast<double>(mag) <= 1e-3);     // sampling_gpu.cu:100-101 (float vs double literal)
 }
 
-// Register-resident FPS: T threads, P points per thread (N <= T*P).
+// Register-resident FPS of one cloud by one workgroup: T threads, P points per thread (N <= T*P).  The indices written are
+// `base` + the index within the cloud (0 for a rectangular batch, the shape's first row for a packed one).
 template <int T, int P, bool LDS_XYZ>
-__global__ __launch_bounds__(T) void fps_reg_kernel(const float *__restrict__ xyz_all, int N, int M,
-                                                    int BS, int log2BS,
-                                                    int32_t *__restrict__ idx_all) {
+__device__ __forceinline__ void fps_reg_body(char *smem, const float *__restrict__ xyz, int N, int M, int BS, int log2BS,
+                                             int32_t *__restrict__ out, int base) {
   constexpr int W = T / 64;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
   long long *slots = reinterpret_cast<long long *>(smem);          // [2][W] (padded to 16*W bytes)
   float4 *sxyz = reinterpret_cast<float4 *>(smem + 16 * (W > 1 ? W : 1));
-
-  const float *xyz = xyz_all + static_cast<size_t>(blockIdx.x) * N * 3;
-  int32_t *out = idx_all + static_cast<size_t>(blockIdx.x) * M;
   const int tid = threadIdx.x;
 
   float px[P], py[P], pz[P], pt[P];
@@ -113,7 +110,7 @@ __global__ __launch_bounds__(T) void fps_reg_kernel(const float *__restrict__ xy
       prio[s] = 0u;
     }
   }
-  if (tid == 0) out[0] = 0;
+  if (tid == 0) out[0] = base;
   if (LDS_XYZ) __syncthreads();
 
   float cx, cy, cz;
@@ -154,24 +151,59 @@ __global__ __launch_bounds__(T) void fps_reg_kernel(const float *__restrict__ xy
     } else {
       cx = xyz[old * 3 + 0]; cy = xyz[old * 3 + 1]; cz = xyz[old * 3 + 2];
     }
-    if (tid == 0) out[j] = old;
+    if (tid == 0) out[j] = base + old;
   }
+}
+
+template <int T, int P, bool LDS_XYZ>
+__global__ __launch_bounds__(T) void fps_reg_kernel(const float *__restrict__ xyz_all, int N, int M,
+                                                    int BS, int log2BS,
+                                                    int32_t *__restrict__ idx_all) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  fps_reg_body<T, P, LDS_XYZ>(smem, xyz_all + static_cast<size_t>(blockIdx.x) * N * 3, N, M, BS, log2BS,
+                              idx_all + static_cast<size_t>(blockIdx.x) * M, 0);
+}
+
+// One cloud of a packed set (ragged.h): its rows, its size and its tie-rule block size BS = min(512, 2^floor(log2 n)) -- the
+// reference's opt_n_threads by integer arithmetic -- all from the offsets on the device.  `n_max` (the host's bound: it sized
+// the workgroup and the LDS copy) caps the row count on top of the offsets' clamp.  false: the shape has no rows; every slot of
+// its output then holds its (clamped) first-row index.
+__device__ __forceinline__ bool fps_ragged_shape(const int32_t *__restrict__ offsets, int cap, int n_max, int M,
+                                                 int32_t *__restrict__ out, int &lo, int &N, int &BS, int &log2BS) {
+  int hi;
+  nsdp::ragged_range(offsets, static_cast<int>(blockIdx.x), cap, lo, hi);
+  N = min(hi - lo, n_max);
+  if (N <= 0) {
+    const int fill = min(lo, cap - 1);
+    for (int j = threadIdx.x; j < M; j += blockDim.x) out[j] = fill;
+    return false;
+  }
+  log2BS = min(9, 31 - __builtin_clz(static_cast<unsigned>(N)));
+  BS = 1 << log2BS;
+  return true;
+}
+
+template <int T, int P, bool LDS_XYZ>
+__global__ __launch_bounds__(T) void fps_reg_ragged_kernel(const float *__restrict__ xyz_packed,
+                                                           const int32_t *__restrict__ offsets, int cap, int n_max, int M,
+                                                           int32_t *__restrict__ idx_all) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  int32_t *out = idx_all + static_cast<size_t>(blockIdx.x) * M;
+  int lo, N, BS, log2BS;
+  if (!fps_ragged_shape(offsets, cap, min(n_max, T * P), M, out, lo, N, BS, log2BS)) return;   // (uniform: before any barrier)
+  fps_reg_body<T, P, LDS_XYZ>(smem, xyz_packed + static_cast<size_t>(lo) * 3, N, M, BS, log2BS, out, lo);
 }
 
 // Generic fallback for very large clouds (N > 8192): running min-distance in global scratch.
 template <int T>
-__global__ __launch_bounds__(T) void fps_big_kernel(const float *__restrict__ xyz_all,
-                                                    float *__restrict__ tmp_all, int N, int M, int BS,
-                                                    int log2BS, int32_t *__restrict__ idx_all) {
+__device__ __forceinline__ void fps_big_body(const float *__restrict__ xyz, float *__restrict__ tmp, int N, int M, int BS,
+                                             int log2BS, int32_t *__restrict__ out, int base) {
   constexpr int W = T / 64;
   __shared__ long long slots[2 * W];
-  const float *xyz = xyz_all + static_cast<size_t>(blockIdx.x) * N * 3;
-  float *tmp = tmp_all + static_cast<size_t>(blockIdx.x) * N;
-  int32_t *out = idx_all + static_cast<size_t>(blockIdx.x) * M;
   const int tid = threadIdx.x;
   for (int k = tid; k < N; k += T)
     tmp[k] = point_valid(xyz[k * 3 + 0], xyz[k * 3 + 1], xyz[k * 3 + 2]) ? 1e10f : -1.0f;
-  if (tid == 0) out[0] = 0;
+  if (tid == 0) out[0] = base;
   float cx = xyz[0], cy = xyz[1], cz = xyz[2];
   for (int j = 1; j < M; ++j) {
     long long best = LLONG_MIN;
@@ -195,8 +227,27 @@ __global__ __launch_bounds__(T) void fps_big_kernel(const float *__restrict__ xy
     }
     const int old = decode_winner(g, log2BS);
     cx = xyz[old * 3 + 0]; cy = xyz[old * 3 + 1]; cz = xyz[old * 3 + 2];
-    if (tid == 0) out[j] = old;
+    if (tid == 0) out[j] = base + old;
   }
+}
+
+template <int T>
+__global__ __launch_bounds__(T) void fps_big_kernel(const float *__restrict__ xyz_all,
+                                                    float *__restrict__ tmp_all, int N, int M, int BS,
+                                                    int log2BS, int32_t *__restrict__ idx_all) {
+  fps_big_body<T>(xyz_all + static_cast<size_t>(blockIdx.x) * N * 3, tmp_all + static_cast<size_t>(blockIdx.x) * N, N, M, BS,
+                  log2BS, idx_all + static_cast<size_t>(blockIdx.x) * M, 0);
+}
+
+// (tmp[cap]: a shape's running distances live at its own rows)
+template <int T>
+__global__ __launch_bounds__(T) void fps_big_ragged_kernel(const float *__restrict__ xyz_packed,
+                                                           const int32_t *__restrict__ offsets, float *__restrict__ tmp, int cap,
+                                                           int n_max, int M, int32_t *__restrict__ idx_all) {
+  int32_t *out = idx_all + static_cast<size_t>(blockIdx.x) * M;
+  int lo, N, BS, log2BS;
+  if (!fps_ragged_shape(offsets, cap, n_max, M, out, lo, N, BS, log2BS)) return;
+  fps_big_body<T>(xyz_packed + static_cast<size_t>(lo) * 3, tmp + lo, N, M, BS, log2BS, out, lo);
 }
 
 // cuda_utils.h:15-19 -- same double arithmetic as the reference host code.
@@ -221,6 +272,19 @@ int launch_reg(const float *xyz, int B, int N, int M, int BS, int log2BS, int32_
   return nsdp::launch_status("fps_reg_kernel");
 }
 
+template <int T, int P, bool LDS_XYZ>
+int launch_reg_ragged(const float *xyz, const int32_t *offsets, int B, int cap, int n_max, int M, int32_t *idx,
+                      hipStream_t st) {
+  constexpr int W = T / 64;
+  const size_t smem = 16 * (W > 1 ? W : 1) + (LDS_XYZ ? static_cast<size_t>(n_max) * 16 : 0);
+  if (smem > 64 * 1024) {
+    NSDP_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&fps_reg_ragged_kernel<T, P, LDS_XYZ>),
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(smem)));
+  }
+  hipLaunchKernelGGL((fps_reg_ragged_kernel<T, P, LDS_XYZ>), dim3(B), dim3(T), smem, st, xyz, offsets, cap, n_max, M, idx);
+  return nsdp::launch_status("fps_reg_ragged_kernel");
+}
+
 }  // namespace
 
 extern "C" int nsdp_furthest_point_sampling(const float *xyz, int B, int N, int nsamples, float *tmp,
@@ -242,4 +306,26 @@ extern "C" int nsdp_furthest_point_sampling(const float *xyz, int B, int N, int 
   hipLaunchKernelGGL((fps_big_kernel<1024>), dim3(B), dim3(1024), 0, st, xyz, tmp, N, nsamples, BS,
                      log2BS, idx_out);
   return nsdp::launch_status("fps_big_kernel");
+}
+
+extern "C" int nsdp_furthest_point_sampling_ragged(const float *xyz_packed, const int32_t *offsets, int B, int cap, int n_max,
+                                                   int nsamples, float *tmp, int32_t *idx_out, void *stream) {
+  if (B <= 0) return 0;
+  NSDP_REQUIRE(nsamples > 0, "fps_ragged: nsamples must be positive (got %d)", nsamples);
+  NSDP_REQUIRE(xyz_packed && offsets && idx_out, "fps_ragged: null pointer");
+  NSDP_REQUIRE(cap > 0 && n_max > 0, "fps_ragged: cap and n_max must be positive (got %d, %d)", cap, n_max);
+  NSDP_REQUIRE(B <= 65535, "fps_ragged: batch %d too large for one launch", B);
+  n_max = n_max < cap ? n_max : cap;
+  NSDP_REQUIRE((static_cast<long long>(n_max) >> kRankShift) == 0, "fps_ragged: n_max too large (%d)", n_max);
+  NSDP_REQUIRE(tmp || n_max <= 8192, "fps_ragged: n_max=%d > 8192 needs the (cap) scratch buffer", n_max);
+  hipStream_t st = nsdp::as_stream(stream);
+  // the number of real rows is known to the device alone: bytes accounted with cap, an upper bound
+  nsdp::prof::Scope scope(nsdp::prof::kFps, st, 0.0, 12.0 * cap + 4.0 * static_cast<double>(B) * nsamples);
+  if (n_max <= 512) return launch_reg_ragged<64, 8, true>(xyz_packed, offsets, B, cap, n_max, nsamples, idx_out, st);
+  if (n_max <= 2048) return launch_reg_ragged<256, 8, true>(xyz_packed, offsets, B, cap, n_max, nsamples, idx_out, st);
+  if (n_max <= 4096) return launch_reg_ragged<512, 8, true>(xyz_packed, offsets, B, cap, n_max, nsamples, idx_out, st);
+  if (n_max <= 8192) return launch_reg_ragged<1024, 8, false>(xyz_packed, offsets, B, cap, n_max, nsamples, idx_out, st);
+  hipLaunchKernelGGL((fps_big_ragged_kernel<1024>), dim3(B), dim3(1024), 0, st, xyz_packed, offsets, tmp, cap, n_max, nsamples,
+                     idx_out);
+  return nsdp::launch_status("fps_big_ragged_kernel");
 }

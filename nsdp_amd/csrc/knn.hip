@@ -12,6 +12,7 @@
 // (contraction off), bit-identical to the reference's torch.sum of squares; order = ascending
 // (distance, index) (torch.argsort is unstable on CPU, so exact ties have no reference order).
 #include <cfloat>
+#include <climits>
 
 #include "common.h"
 #include "prof.h"
@@ -27,10 +28,12 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // One lane's search: `tile` is the workgroup's LDS tile, `qp` the lane's query point (read when `active`), `source` the m
 // points of the lane's shape; the k best go to io[0..k) / dout[0..k) (dout may be NULL).  Every lane of the workgroup must
-// call it (barriers), with the same `source` and `m`.
+// call it (barriers), with the same `source` and `m`.  The indices written are min(idx_base + index within `source`, idx_max):
+// (0, INT_MAX) for a rectangular source, (the shape's first row, cap - 1) for a packed one.
 template <int K>
 __device__ __forceinline__ void knn_scan(float4 *tile, const float *__restrict__ qp, const float *__restrict__ source, int m,
-                                         int k, bool active, int32_t *__restrict__ io, float *__restrict__ dout) {
+                                         int k, bool active, int32_t *__restrict__ io, float *__restrict__ dout,
+                                         int idx_base = 0, int idx_max = INT_MAX) {
   float qx = 0.f, qy = 0.f, qz = 0.f;
   if (active) {
     qx = qp[0]; qy = qp[1]; qz = qp[2];
@@ -76,7 +79,7 @@ __device__ __forceinline__ void knn_scan(float4 *tile, const float *__restrict__
   if (active) {
 #pragma unroll
     for (int t = 0; t < K; ++t)
-      if (t < k) io[t] = bi[t];
+      if (t < k) io[t] = min(bi[t] + idx_base, idx_max);
     if (dout) {
 #pragma unroll
       for (int t = 0; t < K; ++t)
@@ -223,10 +226,14 @@ __global__ __launch_bounds__(256) void knn_split_kernel(const float *__restrict_
 // 16-entry FIFO with the candidates taken four at a time (independent LDS reads and distances) against 8 entries one at a
 // time: 111 against 125 us; eight lanes per query instead of four: slower (124 / 1096 / 2029 us, more list work).  With the
 // tile as three planes + sentinels and the distances on packed fp32 operations (below): 92 / 458 / 767 us.
+// One workgroup's search as a function of what the two kernels below differ in: `qp` the query point of this lane's query
+// (read when `active`; the S lanes of a query pass the same), `source` the m points every lane of the workgroup searches, `io` /
+// `dout` (or NULL) the query's k output slots, and the index written = min(idx_base + index within `source`, idx_max).
 template <int K, int S, int kQueue>
-__global__ __launch_bounds__(256) void knn_split_queue_kernel(const float *__restrict__ query_all,
-                                                              const float *__restrict__ source_all, int n, int m, int k,
-                                                              int32_t *__restrict__ idx_all, float *__restrict__ dist_all) {
+__device__ __forceinline__ void knn_split_queue_scan(const float *__restrict__ qp, bool active,
+                                                     const float *__restrict__ source, int m, int k,
+                                                     int32_t *__restrict__ io, float *__restrict__ dout, int idx_base,
+                                                     int idx_max) {
   // the tile as three planes (four candidates = three 16-byte reads, two distances per packed operation) with 16 sentinel
   // entries behind the last point: x = FLT_MAX squares to +inf, which no threshold admits -- no range checks in the scan
   __shared__ __attribute__((aligned(16))) float tx[kTile + 16];
@@ -235,16 +242,10 @@ __global__ __launch_bounds__(256) void knn_split_queue_kernel(const float *__res
   __shared__ float md[256 * K];      // the FIFOs during the scan ([slot][thread]: conflict-free), the S lists afterwards
   __shared__ int mi[256 * K];
   static_assert(K >= kQueue, "the FIFOs live in the merge buffers");
-  constexpr int kQ = 256 / S;
-  const int b = blockIdx.y;
-  const float *query = query_all + static_cast<size_t>(b) * n * 3;
-  const float *source = source_all + static_cast<size_t>(b) * m * 3;
-  const int ql = threadIdx.x / S, sub = threadIdx.x - ql * S;
-  const int i = blockIdx.x * kQ + ql;
-  const bool active = i < n;
+  const int sub = threadIdx.x % S;
   float qx = 0.f, qy = 0.f, qz = 0.f;
   if (active) {
-    qx = query[i * 3 + 0]; qy = query[i * 3 + 1]; qz = query[i * 3 + 2];
+    qx = qp[0]; qy = qp[1]; qz = qp[2];
   }
   float bd[K];
   int bi[K];
@@ -336,8 +337,6 @@ __global__ __launch_bounds__(256) void knn_split_queue_kernel(const float *__res
     int head[S];
 #pragma unroll
     for (int u = 0; u < S; ++u) head[u] = 0;
-    int32_t *io = idx_all + (static_cast<size_t>(b) * n + i) * k;
-    float *dout = dist_all ? dist_all + (static_cast<size_t>(b) * n + i) * k : nullptr;
     for (int t = 0; t < k; ++t) {
       float best_d = FLT_MAX;
       int best_i = 0x7fffffff, best_u = 0;
@@ -352,11 +351,82 @@ __global__ __launch_bounds__(256) void knn_split_queue_kernel(const float *__res
       }
 #pragma unroll
       for (int u = 0; u < S; ++u) head[u] += (u == best_u) ? 1 : 0;
-      io[t] = best_i;
+      // (an empty slot -- fewer than k source points, which only a packed source with corrupt offsets can have -- names the
+      // source's first point)
+      io[t] = min((best_i == 0x7fffffff ? 0 : best_i) + idx_base, idx_max);
       if (dout) dout[t] = best_d;
     }
   }
 }
+
+template <int K, int S, int kQueue>
+__global__ __launch_bounds__(256) void knn_split_queue_kernel(const float *__restrict__ query_all,
+                                                              const float *__restrict__ source_all, int n, int m, int k,
+                                                              int32_t *__restrict__ idx_all, float *__restrict__ dist_all) {
+  constexpr int kQ = 256 / S;
+  const int b = blockIdx.y;
+  const int i = blockIdx.x * kQ + threadIdx.x / S;
+  const size_t row = static_cast<size_t>(b) * n + i;
+  knn_split_queue_scan<K, S, kQueue>(query_all + row * 3, i < n, source_all + static_cast<size_t>(b) * m * 3, m, k,
+                                     idx_all + row * k, dist_all ? dist_all + row * k : nullptr, 0, INT_MAX);
+}
+
+// Both searches against a PACKED source set (ragged.h): source [cap,3] + offsets [B+1] on the device, shape b's queries search
+// rows offsets[b] .. offsets[b+1] (clamped as ragged.h clamps them, and to n_max rows) and get packed-row indices.  The queries
+// are rectangular [B,n,3] (query_offsets NULL: the shape is the grid's y index) or packed themselves ([qcap,3] +
+// query_offsets: kQ queries of a workgroup belong to one shape, surplus workgroups return as a whole before any barrier, rows
+// at or beyond query_offsets[B] are not written).  `row` never leaves the query buffer: inactive lanes take the last row of
+// their shape.
+template <int kQ>
+__device__ __forceinline__ bool knn_rs_tile(const int32_t *__restrict__ query_offsets, const int32_t *__restrict__ offsets, int B,
+                                            int n, int qcap, int cap, int n_max, int ql, size_t &row, bool &active, int &lo,
+                                            int &m) {
+  int b, row0, end;
+  if (query_offsets) {
+    if (!nsdp::ragged_tile<kQ>(query_offsets, B, qcap, static_cast<int>(blockIdx.x), b, row0, end)) return false;
+    active = row0 + ql < end;
+    row = static_cast<size_t>(active ? row0 + ql : end - 1);
+  } else {
+    b = blockIdx.y;
+    const int i = blockIdx.x * kQ + ql;
+    active = i < n;
+    row = static_cast<size_t>(b) * n + (active ? i : n - 1);
+  }
+  int hi;
+  nsdp::ragged_range(offsets, b, cap, lo, hi);
+  m = min(hi - lo, n_max);
+  return true;
+}
+
+template <int K, int S, int kQueue>
+__global__ __launch_bounds__(256) void knn_rs_split_queue_kernel(const float *__restrict__ query,
+                                                                 const int32_t *__restrict__ query_offsets,
+                                                                 const float *__restrict__ source,
+                                                                 const int32_t *__restrict__ offsets, int B, int n, int qcap,
+                                                                 int cap, int n_max, int k, int32_t *__restrict__ idx_all,
+                                                                 float *__restrict__ dist_all) {
+  size_t row;
+  bool active;
+  int lo, m;
+  if (!knn_rs_tile<256 / S>(query_offsets, offsets, B, n, qcap, cap, n_max, threadIdx.x / S, row, active, lo, m)) return;
+  knn_split_queue_scan<K, S, kQueue>(query + row * 3, active, source + static_cast<size_t>(lo) * 3, m, k, idx_all + row * k,
+                                     dist_all ? dist_all + row * k : nullptr, lo, cap - 1);
+}
+
+template <int K>
+__global__ __launch_bounds__(256) void knn_rs_kernel(const float *__restrict__ query, const int32_t *__restrict__ query_offsets,
+                                                     const float *__restrict__ source, const int32_t *__restrict__ offsets,
+                                                     int B, int n, int qcap, int cap, int n_max, int k,
+                                                     int32_t *__restrict__ idx_all, float *__restrict__ dist_all) {
+  __shared__ float4 tile[kTile];
+  size_t row;
+  bool active;
+  int lo, m;
+  if (!knn_rs_tile<256>(query_offsets, offsets, B, n, qcap, cap, n_max, threadIdx.x, row, active, lo, m)) return;
+  knn_scan<K>(tile, query + row * 3, source + static_cast<size_t>(lo) * 3, m, k, active, idx_all + row * k,
+              dist_all ? dist_all + row * k : nullptr, lo, cap - 1);
+}
+
 
 int g_knn_queue = 1;      // nsdp_debug_set(10, v), NSDP_KNN_QUEUE: 0 = the immediate-insertion kernel (A/B)
 
@@ -393,6 +463,28 @@ int launch_ragged(const float *q, const int32_t *offsets, const float *s, int B,
   const int tiles = static_cast<int>(nsdp::ragged_max_tiles(cap, B, 256));
   hipLaunchKernelGGL((knn_ragged_kernel<K>), dim3(tiles), dim3(256), 0, st, q, offsets, s, B, cap, m, k, idx, d2);
   return nsdp::launch_status("knn_ragged_kernel");
+}
+
+// the form is chosen as `launch` chooses it, from what the host knows: the number of query rows (B * n, or the capacity of a
+// packed query set) and the bound of a shape's source rows
+template <int K>
+int launch_rs(const float *q, const int32_t *qoff, const float *s, const int32_t *offsets, int B, int n, int qcap, int cap,
+              int n_max, int k, int32_t *idx, float *d2, hipStream_t st) {
+  const long long rows = qoff ? qcap : static_cast<long long>(B) * n;
+  if constexpr (K <= 16) {
+    if (n_max >= 256 && (rows + 255) / 256 * 4 < 8LL * nsdp::num_cus()) {
+      constexpr int kQueue = K >= 16 ? 16 : 8;
+      NSDP_TRACE("knn_rs_split_queue<%d,4,%d>", K, kQueue);
+      const dim3 grid = qoff ? dim3(static_cast<unsigned>(nsdp::ragged_max_tiles(qcap, B, 64))) : dim3(nsdp::ceil_div(n, 64), B);
+      hipLaunchKernelGGL((knn_rs_split_queue_kernel<K, 4, kQueue>), grid, dim3(256), 0, st, q, qoff, s, offsets, B, n, qcap, cap,
+                         n_max, k, idx, d2);
+      return nsdp::launch_status("knn_rs_split_queue_kernel");
+    }
+  }
+  NSDP_TRACE("knn_rs<%d>", K);
+  const dim3 grid = qoff ? dim3(static_cast<unsigned>(nsdp::ragged_max_tiles(qcap, B, 256))) : dim3(nsdp::ceil_div(n, 256), B);
+  hipLaunchKernelGGL((knn_rs_kernel<K>), grid, dim3(256), 0, st, q, qoff, s, offsets, B, n, qcap, cap, n_max, k, idx, d2);
+  return nsdp::launch_status("knn_rs_kernel");
 }
 
 }  // namespace
@@ -433,4 +525,24 @@ extern "C" int nsdp_knn_ragged(const float *query, const int32_t *offsets, const
   if (k <= 16) return launch_ragged<16>(query, offsets, source, B, cap, m, k, idx_out, dist2_out, st);
   if (k <= 32) return launch_ragged<32>(query, offsets, source, B, cap, m, k, idx_out, dist2_out, st);
   return launch_ragged<64>(query, offsets, source, B, cap, m, k, idx_out, dist2_out, st);
+}
+
+extern "C" int nsdp_knn_ragged_source(const float *query, const int32_t *query_offsets, const float *source,
+                                      const int32_t *offsets, int B, int n, int qcap, int cap, int n_max, int k, int32_t *idx_out,
+                                      float *dist2_out, void *stream) {
+  const long long rows = query_offsets ? static_cast<long long>(qcap) : static_cast<long long>(B) * n;
+  if (B <= 0 || rows <= 0 || k <= 0) return 0;
+  NSDP_REQUIRE(query && source && offsets && idx_out, "knn_ragged_source: null pointer");
+  NSDP_REQUIRE(cap > 0 && n_max > 0, "knn_ragged_source: cap and n_max must be positive (got %d, %d)", cap, n_max);
+  NSDP_REQUIRE(k <= n_max, "knn_ragged_source: k=%d exceeds the bound of a shape's source points n_max=%d", k, n_max);
+  NSDP_REQUIRE(k <= 64, "knn_ragged_source: k=%d > 64 is not supported", k);
+  NSDP_REQUIRE(B <= 65535, "knn_ragged_source: batch %d too large for one launch", B);
+  NSDP_REQUIRE(rows * k < (1LL << 31), "knn_ragged_source: %lld query rows x k=%d too large", rows, k);
+  hipStream_t st = nsdp::as_stream(stream);
+  nsdp::prof::Scope scope(nsdp::prof::kKnn, st, 0.0,
+                          12.0 * (static_cast<double>(rows) + cap) + 4.0 * rows * k * (dist2_out ? 2 : 1));
+  if (k <= 8) return launch_rs<8>(query, query_offsets, source, offsets, B, n, qcap, cap, n_max, k, idx_out, dist2_out, st);
+  if (k <= 16) return launch_rs<16>(query, query_offsets, source, offsets, B, n, qcap, cap, n_max, k, idx_out, dist2_out, st);
+  if (k <= 32) return launch_rs<32>(query, query_offsets, source, offsets, B, n, qcap, cap, n_max, k, idx_out, dist2_out, st);
+  return launch_rs<64>(query, query_offsets, source, offsets, B, n, qcap, cap, n_max, k, idx_out, dist2_out, st);
 }

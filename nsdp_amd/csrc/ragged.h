@@ -39,6 +39,15 @@ __device__ __forceinline__ bool ragged_tile(const int32_t *__restrict__ offsets,
   return false;
 }
 
+// Rows [lo, hi) of shape b (0 <= b < B) of a packed set, clamped like ragged_tile clamps them: 0 <= lo <= hi <= cap whatever
+// `offsets` holds.  `b` must be uniform over the wave; a few scalar loads.
+__device__ __forceinline__ void ragged_range(const int32_t *__restrict__ offsets, int b, int cap, int &lo, int &hi) {
+  int l = min(max(offsets[0], 0), cap);
+  for (int s = 0; s < b; ++s) l = min(max(offsets[s + 1], l), cap);
+  lo = __builtin_amdgcn_readfirstlane(l);
+  hi = __builtin_amdgcn_readfirstlane(min(max(offsets[b + 1], l), cap));
+}
+
 // upper bound of the tiles of a packed set of `cap` rows in B shapes (see above)
 inline long long ragged_max_tiles(long long cap, long long B, int tile) { return (cap + tile - 1) / tile + B; }
 

@@ -28,6 +28,17 @@ interleaved repetitions (median; every repetition in ``*_reps``): ``ms_ragged`` 
 rectangular call at B x max(counts), replayed under ``--graph``), ``ms_per_shape_loop`` (B eager calls at batch 1, the only
 exact alternative without the packed form) and ``equal_to_padded`` (every shape's rows bit-equal to the padded call's).
 ``--out DIR``: verts_tgt_pred.npy is the packed [total, 3] array, verts_offsets.npy the [B + 1] offsets.
+
+    python -m nsdp_amd.infer CONFIG --surface-counts n1,n2,... [--vertex-counts ...|--queries NQ] [--decoder-dtype f32|bf16] ...
+
+Surface clouds of DIFFERENT sample counts in one call (one GPU, eager): B = the number of counts, shape b brings the first n_b
+rows of the synthetic max(counts)-sample cloud; the encoder's levels are capped at min(counts).  The mesh vertices are ragged
+too (``--vertex-counts``, as many counts) or NQ per shape.  The line gains ``ragged_surface``, ``surface_counts``,
+``ms_per_call``, ``ms_per_shape_loop`` (B eager calls at batch 1 -- a surface cloud cannot be padded, so this is the only
+exact alternative; interleaved repetitions, median, as above) and ``l2_vs_per_shape_loop`` (max over shapes of the RMS point
+distance between the two vertex predictions: reported, not asserted -- the dense layers pick tile shapes from the row count, so
+the two are close, not bit-equal).  ``--out DIR``: surface_samples_tgt_pred.npy is the packed [total, 3] array with
+surface_offsets.npy; verts_tgt_pred.npy is packed with verts_offsets.npy under ``--vertex-counts``, else [B, NQ, 3].
 """
 from __future__ import annotations
 
@@ -74,6 +85,8 @@ def build_parser():
     ap.add_argument("--out", default=None, help="directory for rank 0's predictions (<key>.npy)")
     ap.add_argument("--vertex-counts", default=None,
                     help="comma-separated vertex counts, one per shape: decode the meshes as one packed (ragged) set")
+    ap.add_argument("--surface-counts", default=None,
+                    help="comma-separated surface sample counts, one per shape: encode the clouds as one packed (ragged) set")
     ap.add_argument("--capacity", type=int, default=None,
                     help="rows of the packed vertex buffer (default: the sum of --vertex-counts); a captured graph serves every "
                          "batch of as many shapes whose vertices sum to at most this")
@@ -159,11 +172,101 @@ def _ragged(args, config, model, test_fn, dd, counts, ns):
     return 0
 
 
+def _ragged_surface(args, config, model, test_fn, dd, scounts, vcounts):
+    """The --surface-counts run (one GPU, eager): the timed packed step, then B calls at batch 1, interleaved."""
+    import statistics
+    import numpy as np
+    import torch
+    from . import hip_decoder
+    from .ragged import RaggedPoints
+    B = len(scounts)
+    surf = RaggedPoints.from_rows([dd["surface_samples_inputs"][b, :n] for b, n in enumerate(scounts)])
+    rdd = {"surface_samples_inputs": surf, "surface_samples_src": surf.columns(0, 3)}
+    if vcounts:
+        rdd["verts_src"] = RaggedPoints.from_list([dd["verts_src"][b, :n] for b, n in enumerate(vcounts)])
+    else:
+        rdd["verts_src"] = dd["verts_src"]
+    nverts = vcounts or [int(dd["verts_src"].shape[1])] * B
+    per_shape = [{"surface_samples_inputs": dd["surface_samples_inputs"][b:b + 1, :n].contiguous(),
+                  "surface_samples_src": dd["surface_samples_inputs"][b:b + 1, :n, 0:3].contiguous(),
+                  "verts_src": dd["verts_src"][b:b + 1, :nverts[b]].contiguous()} for b, n in enumerate(scounts)]
+    loop_out = [None] * B
+
+    def run_ragged():
+        test_fn(model, rdd, config)
+
+    def run_loop():
+        for b, one in enumerate(per_shape):
+            loop_out[b] = test_fn(model, dict(one), config)[1]["verts_tgt_pred"]
+
+    def timed(fn, n):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        for _ in range(n):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / max(1, n)
+
+    for _ in range(args.warmup):
+        run_ragged()
+    ms = timed(run_ragged, args.steps)
+    run_loop()
+    pred = rdd["verts_tgt_pred"]
+    rows = pred.split() if vcounts else [pred[b] for b in range(B)]
+    l2 = max(float((rows[b].double() - loop_out[b][0].double()).pow(2).sum(-1).mean().sqrt()) for b in range(B) if nverts[b])
+    reps = {"ms_ragged": [], "ms_per_shape_loop": []}
+    for _ in range(max(1, args.reps)):
+        reps["ms_ragged"].append(timed(run_ragged, args.steps))
+        reps["ms_per_shape_loop"].append(timed(run_loop, args.steps))
+    if args.out:
+        os.makedirs(args.out, exist_ok=True)
+        np.save(os.path.join(args.out, "surface_samples_tgt_pred.npy"), rdd["surface_samples_tgt_pred"].packed.cpu().numpy())
+        np.save(os.path.join(args.out, "surface_offsets.npy"), surf.offsets.cpu().numpy())
+        np.save(os.path.join(args.out, "verts_tgt_pred.npy"), (pred.packed if vcounts else pred).cpu().numpy())
+        if vcounts:
+            np.save(os.path.join(args.out, "verts_offsets.npy"), pred.offsets.cpu().numpy())
+    total_v = sum(nverts)
+    line = {"metric": "dense_inference_ragged_surface", "model_type": config["model"]["type"], "world": 1, "graph": False,
+            "ragged_surface": True, "surface_counts": scounts, "surface_total": sum(scounts), "ragged": bool(vcounts),
+            "vertex_counts": vcounts or None, "queries": None if vcounts else nverts[0], "total": total_v, "batch": B,
+            "levels": config["model"]["encoder_kwargs"]["npoints_per_layer"], "steps": args.steps, "warmup": args.warmup,
+            "reps": max(1, args.reps), "decoder_dtype": hip_decoder.MODE, "ms_per_call": round(ms, 4),
+            "query_points_per_s": round(total_v / (ms / 1e3), 1) if ms > 0 else None,
+            **{k: round(statistics.median(v), 4) for k, v in reps.items()},
+            **{k + "_reps": [round(x, 4) for x in v] for k, v in reps.items()},
+            "l2_vs_per_shape_loop": l2}
+    print(json.dumps(line), flush=True)
+    return 0
+
+
+def _counts_arg(flag, text, positive=False):
+    try:
+        counts = [int(c) for c in text.split(",") if c.strip() != ""]
+    except ValueError:
+        counts = []
+    if not counts or min(counts) < (1 if positive else 0) or max(counts) == 0:
+        sys.exit(f"nsdp_amd.infer: {flag} wants {'positive' if positive else 'non-negative'} integers n1,n2,..."
+                 f"{'' if positive else ' (not all zero)'}, got {text!r}")
+    return counts
+
+
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     ap = build_parser()
     args = ap.parse_args(argv)
-    counts = None
+    counts = scounts = None
+    if args.surface_counts is not None:
+        scounts = _counts_arg("--surface-counts", args.surface_counts, positive=True)
+        if args.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            sys.exit("nsdp_amd.infer: --surface-counts runs on one GPU (ragged surface clouds are not split over ranks)")
+        if args.graph:
+            sys.exit("nsdp_amd.infer: --surface-counts runs eagerly (a step over ragged surface clouds is not captured)")
+        if args.batch is not None and args.batch != len(scounts):
+            sys.exit(f"nsdp_amd.infer: --batch {args.batch} against {len(scounts)} surface counts")
+        if args.surface is not None and args.surface != max(scounts):
+            sys.exit(f"nsdp_amd.infer: --surface {args.surface} against --surface-counts whose largest is {max(scounts)}")
     if args.vertex_counts is not None:
         try:
             counts = [int(c) for c in args.vertex_counts.split(",") if c.strip() != ""]
@@ -177,6 +280,8 @@ def main(argv=None):
             sys.exit(f"nsdp_amd.infer: --capacity {args.capacity} is below the {sum(counts)} vertices of --vertex-counts")
         if args.batch is not None and args.batch != len(counts):
             sys.exit(f"nsdp_amd.infer: --batch {args.batch} against {len(counts)} vertex counts")
+        if scounts and len(scounts) != len(counts):
+            sys.exit(f"nsdp_amd.infer: {len(scounts)} surface counts against {len(counts)} vertex counts")
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         from .train import launch_ranks
@@ -214,11 +319,11 @@ def main(argv=None):
     from .model import build_model
     from .query_shard import QueryShards, query_sharded
     config = load_config(args.config_file)
-    batch = len(counts) if counts else (args.batch or int(config.get("test", {}).get("batch_size", 1) or 1))
-    ns = args.surface or int(config.get("data", {}).get("num_surf_samples", 0) or
+    batch = len(scounts or counts) if (scounts or counts) else (args.batch or int(config.get("test", {}).get("batch_size", 1) or 1))
+    ns = max(scounts) if scounts else args.surface or int(config.get("data", {}).get("num_surf_samples", 0) or
                              config["model"]["encoder_kwargs"]["npoints_per_layer"][0])
     nq = max(counts) if counts else int(args.queries)
-    _pyramid(config, ns)
+    _pyramid(config, min(scounts) if scounts else ns)      # (ragged surface clouds: the smallest one bounds the levels)
     model, _, _, test_fn = build_model(config, weight_file=args.weight_file, device="cpu")
     if args.weight_file is None:
         state = synth.procedural_state_dict(model.state_dict(), SEED_WEIGHTS)
@@ -229,6 +334,8 @@ def main(argv=None):
     dd["surface_samples_src"] = dd["surface_samples_inputs"][:, :, 0:3].contiguous()
     dd["verts_src"], dd["verts_tgt"] = dd.pop("space_samples_src"), dd.pop("space_samples_tgt")
 
+    if scounts:
+        return _ragged_surface(args, config, model, test_fn, dd, scounts, counts)
     if counts:
         return _ragged(args, config, model, test_fn, dd, counts, ns)
     shards = QueryShards(rank, world)

@@ -47,6 +47,9 @@ class Deformation_Networks(nn.Module):
         when ``training``), on the current stream.  forward(geometry=) takes it instead of searching: a host that knows the next
         batch computes this beside the current step (nsdp_amd.graph_step.PipelinedGeometry) -- FPS is a chain of ~600 dependent
         iterations that no batch size shortens.  ``points`` must be the very tensor forward() is then called with."""
+        if isinstance(surface_samples_inputs, RaggedPoints):
+            raise ValueError("ragged surface cloud refused: geometry() / PipelinedGeometry compute the index sets of rectangular "
+                             "clouds only")
         x = surface_samples_inputs[:, :, 0:3].contiguous() if self.no_input_corr else surface_samples_inputs
         if not (hasattr(self.encoder, "geometry") and hasattr(self.decoder, "geometry")):
             raise NotImplementedError("geometry(): this encoder / decoder pair searches inside its forward pass only")
@@ -60,7 +63,15 @@ class Deformation_Networks(nn.Module):
         the query points.  Callers that decode several query sets against ONE cloud (FlowArbitrary, the dense-inference step
         functions) encode once and call decode() per set; the reference re-runs the whole module each time.
         ``queries``: the points decode() will be called with next -- the decoder's anchor-only work is then launched beside the
-        encoder's forward chain (CrossTransformerDecoder.prefetch, NSDP_DECODER_PREFETCH=0 switches it off)."""
+        encoder's forward chain (CrossTransformerDecoder.prefetch, NSDP_DECODER_PREFETCH=0 switches it off).
+        ``surface_samples_inputs`` may be a RaggedPoints of [total, C] rows (clouds of different sample counts, nsdp_amd.ragged):
+        inference only, refused with its reason where it cannot run (ragged_surface_refusal)."""
+        if isinstance(surface_samples_inputs, RaggedPoints):
+            why = self.ragged_surface_refusal(geometry)
+            if why is not None:
+                raise ValueError("ragged surface cloud refused: " + why)
+            surface_samples_inputs.counts      # (read back once, here: a column view made below shares the host copy)
+            return self.encoder(surface_samples_inputs.columns(0, 3) if self.no_input_corr else surface_samples_inputs)
         x = surface_samples_inputs[:, :, 0:3].contiguous() if self.no_input_corr else surface_samples_inputs
         if geometry is not None:
             enc = self.encoder(x, geometry=geometry["encoder"])
@@ -70,6 +81,24 @@ class Deformation_Networks(nn.Module):
                 and "on_anchors" in inspect.signature(self.encoder.forward).parameters):
             return self.encoder(x, on_anchors=lambda anchors, after: self.decoder.prefetch(queries, anchors, after))
         return self.encoder(x)
+
+    def ragged_surface_refusal(self, geometry=None):
+        """Why this network cannot encode a packed surface cloud right now (None: it can): what the encoder's ragged first level
+        and the ragged decoder (hip_decoder.ragged_refusal: it decodes the surface samples) refuse, named."""
+        from .. import hip_decoder
+        from .encoder.pointransformer import PointTransformerEncoder
+        if geometry is not None:
+            return "geometry= (index sets computed ahead of the pass, PipelinedGeometry) exists for rectangular clouds only"
+        if not isinstance(self.encoder, PointTransformerEncoder):
+            return f"the {type(self.encoder).__name__} encoder (pointnet++ alternate) has no ragged first level"
+        if torch.is_grad_enabled():
+            return "autograd is enabled: ragged surface clouds are inference only -- call under torch.no_grad()"
+        if self.training or self.encoder.training:
+            return ("the model is in training mode: BatchNorm would take batch statistics over the packed rows of all shapes -- "
+                    "call model.eval() first")
+        return hip_decoder.ragged_refusal(self.decoder) if hip_decoder.supported(self.decoder) else (
+            "decoder geometry: the packed surface samples are decoded by the fused kernels, built for dim=200, hidden_dim=128, "
+            "n_blocks=5, out_dim=3")
 
     def decode(self, points, encoding):
         """points [B,NQ,3] -> [B,NQ,3]; a RaggedPoints (meshes of different sizes, nsdp_amd.ragged) -> a RaggedPoints."""
@@ -125,11 +154,23 @@ def l2_error_of(pred, target):
     return compute_l2_error(pred, target)
 
 
+def check_ragged_surface(inputs, src):
+    """A ragged ``surface_samples_inputs`` goes with a ``surface_samples_src`` packed over the same offsets (and a rectangular
+    one with a tensor): the step functions decode the source samples against the encoding of the inputs, shape by shape."""
+    if isinstance(inputs, RaggedPoints) != isinstance(src, RaggedPoints):
+        raise ValueError("surface_samples_inputs and surface_samples_src must both be RaggedPoints or both be tensors")
+    if isinstance(inputs, RaggedPoints) and not inputs.same_layout(src):
+        raise ValueError(f"surface_samples_src ({src!r}) is not packed like surface_samples_inputs ({inputs!r})")
+
+
 @torch.no_grad()
 def test_on_batch_with_cano(model, data_dict, config, compute_loss=False):
     """Dense inference: surface samples, then all mesh vertices (reference :90-109).  ``data_dict["verts_src"]`` may be a
-    RaggedPoints (meshes of different vertex counts, packed): ``verts_tgt_pred`` is then one too."""
+    RaggedPoints (meshes of different vertex counts, packed): ``verts_tgt_pred`` is then one too.  Independently,
+    ``surface_samples_inputs`` may be a RaggedPoints of [total, 7] rows (clouds of different sample counts) with
+    ``surface_samples_src`` packed over the same offsets: ``surface_samples_tgt_pred`` then comes back as a RaggedPoints."""
     inputs = data_dict["surface_samples_inputs"]
+    check_ragged_surface(inputs, data_dict["surface_samples_src"])
     if ENCODE_ONCE:
         # the reference runs the module twice on the same surface input (:96, :101): same encoding both times
         encoding = model.encode(inputs)

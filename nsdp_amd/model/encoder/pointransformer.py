@@ -5,12 +5,16 @@ import torch
 import torch.nn as nn
 
 from .. import ops
-from .blocks import ElementwiseMLP, TransformerBlock, TransitionDown
+from ... import precision
+from ...ragged import RaggedPoints
+from .blocks import ElementwiseMLP, TransformerBlock, TransformerSetAbstraction, TransitionDown
 
 
 class PointTransformerEncoder(nn.Module):
     """input [B,N,3(+F)] -> {'z': [B,d], 'anchors': [B,n_last,3], 'anchor_feats': [B,n_last,d]}
-    (reference model/encoder/pointransformer.py:27-140; same constructor kwargs and state_dict keys)."""
+    (reference model/encoder/pointransformer.py:27-140; same constructor kwargs and state_dict keys).
+    The input may be a RaggedPoints of [total,3(+F)] rows -- B clouds of different sample counts (nsdp_amd.ragged), eval mode
+    and no autograd: the first level runs over the packed rows, everything below it is the rectangular code."""
 
     def __init__(self, npoints_per_layer, nneighbor, nneighbor_reduced, nfinal_transformers,
                  d_transformer, d_reduced, full_SA=False, has_features=False, inp_feat_dim=1):
@@ -79,6 +83,11 @@ class PointTransformerEncoder(nn.Module):
         ENQUEUED -- on the pyramid's stream ``after``, ~1 ms into a step -- so that work which needs nothing else of the encoding
         (the decoder's anchor search and position encoding, CrossTransformerDecoder.prefetch) can be launched beside the
         encoder's forward chain.  Whatever it returns travels in the encoding as ``'prefetch'``."""
+        if isinstance(xyz, RaggedPoints):
+            if on_anchors is not None or geometry is not None:
+                raise ValueError("ragged surface cloud refused: geometry= / on_anchors= (index sets computed ahead of the pass, "
+                                 "PipelinedGeometry) exist for rectangular clouds only")
+            return self._forward_ragged(xyz)
         coords = xyz[:, :, :3].contiguous() if self.has_features else xyz
         # all FPS / kNN index tensors of the pyramid, launched on a side stream under transformer_begin
         begin = {}
@@ -97,8 +106,71 @@ class PointTransformerEncoder(nn.Module):
         else:
             feats = self.transformer_begin(xyz, **begin)
         join()
+        return self._below_begin(xyz, feats, levels, geometry, prefetch)
+
+    def ragged_refusal(self, cloud):
+        """Why a packed surface cloud cannot be encoded right now (None: it can)."""
+        if torch.is_grad_enabled():
+            return "autograd is enabled: the ragged first level is inference only -- call under torch.no_grad()"
+        if self.training:
+            return ("the model is in training mode: BatchNorm would take batch statistics over the packed rows of all shapes, "
+                    "which is not what a batch of clouds of different sizes means -- call model.eval() first")
+        if precision.is_bf16():
+            return "bf16 storage (NSDP_STORAGE=bf16): the ragged first level is built and tested in fp32 storage only"
+        if not self.transition_downs or not all(isinstance(td.sa, TransformerSetAbstraction) for td in self.transition_downs[:1]):
+            return "this encoder has no attentive first down-sampling level to make ragged"
+        if cloud.packed.dim() != 2 or cloud.packed.shape[1] != (3 + self.enc_sdf.in_features if self.has_features else 3):
+            return (f"rows of {cloud.packed.shape[1]} columns against an encoder of "
+                    f"{3 + self.enc_sdf.in_features if self.has_features else 3} input channels")
+        if cloud.packed.dtype is not torch.float32:
+            return f"packed rows must be float32, got {cloud.packed.dtype}"
+        return None
+
+    def _forward_ragged(self, cloud):
+        """forward() for B clouds of different sample counts, packed: transformer_begin and the first set abstraction run on the
+        tight rows as ONE shape [1,total,.] with per-shape index sets (ops.geometry_pyramid_ragged: every neighbour of a row is a
+        row of its own shape), the abstraction's output is [B,n1,d], and the rest is the rectangular code.  Eval-mode BatchNorm
+        is a per-row affine map, so every shape gets what its own batch-1 call gives it."""
+        why = self.ragged_refusal(cloud)
+        if why is not None:
+            raise ValueError("ragged surface cloud refused: " + why)
+        counts = cloud.counts                      # (host counts: read back once if the set was built from device offsets alone)
+        npoints, ks, _ = self._pyramid_args()
+        tb, B, total = self.transformer_begin, cloud.batch, sum(counts)
+        for b, n in enumerate(counts):
+            if n == 0:
+                raise ValueError(f"ragged surface cloud: shape {b} is empty (0 samples)")
+            if n < npoints[0]:
+                raise ValueError(f"ragged surface cloud: shape {b} has {n} samples, fewer than the {npoints[0]} points the first "
+                                 "level samples (npoints_per_layer[1])")
+            for what, k in (("first attention block", None if tb.group_all else tb.k), ("first set abstraction", ks[0][0])):
+                if k is not None and n < k:
+                    raise ValueError(f"ragged surface cloud: shape {b} has {n} samples, fewer than the {k} neighbours of the {what}")
+        if tb.group_all:
+            raise ValueError("ragged surface cloud refused: a first block that attends to the whole cloud (group_all) has no ragged form")
+        rows = cloud.packed[:total]                # the tight view: the encoder's dense layers see real rows only
+        offsets = cloud.offsets
+        coords = rows[:, :3].contiguous() if self.has_features else rows.contiguous()
+        begin_idx, levels, join = ops.geometry_pyramid_ragged(coords, offsets, max(counts), tb.k, npoints, ks)
+        xyz = coords.view(1, total, 3)
+        if self.has_features:
+            feats = tb(xyz, ops.linear(rows[:, 3:].unsqueeze(0), self.enc_sdf), idx=begin_idx)
+        else:
+            feats = tb(xyz, idx=begin_idx)
+        join()
+        n1 = npoints[0]
+        _, down = self.transition_downs[0](xyz, feats, levels[0])              # query side [1,B*n1,.] against [1,total,.]
+        entered = (levels[0]["new_xyz"].view(B, n1, 3), down.reshape(B, n1, down.shape[-1]))
+        return self._below_begin(None, None, levels, None, None, entered=entered)
+
+    def _below_begin(self, xyz, feats, levels, geometry, prefetch, entered=None):
+        """Everything below transformer_begin.  ``entered``: (centres [B,n1,3], features [B,n1,d]) when the first transition down
+        has already run (the ragged first level)."""
         for i in range(len(self.transition_downs)):
-            xyz, feats = self.transition_downs[i](xyz, feats, levels[i])
+            if i == 0 and entered is not None:
+                xyz, feats = entered
+            else:
+                xyz, feats = self.transition_downs[i](xyz, feats, levels[i])
             feats = self.elementwise_extras[i](feats)
             feats = self.transformer_downs[i](xyz, feats, idx=levels[i]["blk_idx"], inv=levels[i].get("blk_inv"))
             if i == 0 and self.d_reduced != self.d_transformer:

@@ -65,6 +65,9 @@ class FlowArbitrary(nn.Module):
         return net.decode(queries, encoding)
 
     def deform_input(self, surf_src2cano, surface_samples_tgt, cano_handle_sample_mask):
+        if isinstance(surf_src2cano, RaggedPoints):      # ragged surface clouds: the packed [capacity, 7] concatenation
+            return surf_src2cano.like(torch.cat([surf_src2cano.packed, surface_samples_tgt.packed,
+                                                 cano_handle_sample_mask.packed], dim=-1))
         return torch.cat([surf_src2cano, surface_samples_tgt, cano_handle_sample_mask], dim=-1).contiguous()
 
     def forward(self, space_samples_src, surface_samples_src, surface_samples_tgt, cano_handle_sample_mask):
@@ -75,6 +78,11 @@ class FlowArbitrary(nn.Module):
 
 def _split(data_dict):
     s = data_dict["surface_samples_inputs"]
+    if isinstance(s, RaggedPoints):      # ragged surface clouds: three packed sets over the same offsets
+        if s.packed.shape[1] != 7:
+            raise ValueError(f"ragged surface_samples_inputs must be [total, 7] rows, got {tuple(s.packed.shape)}")
+        s.counts      # (read back once if the set came with device offsets alone: the three views share the host copy)
+        return s.columns(0, 3), s.columns(3, 6), s.columns(6, 7)
     return s[:, :, 0:3], s[:, :, 3:6], s[:, :, 6:7]
 
 
@@ -114,14 +122,17 @@ def validate_on_batch_with_arbitrary(model, data_dict, config):
 @torch.no_grad()
 def test_on_batch_with_arbitrary(model, data_dict, config, compute_loss=False):
     """reference model/flow_arbitrary.py:65-85.  ``data_dict["verts_src"]`` may be a RaggedPoints (meshes of different vertex
-    counts, packed): both networks decode it ragged and ``verts_tgt_pred`` is one."""
+    counts, packed): both networks decode it ragged and ``verts_tgt_pred`` is one.  ``surface_samples_inputs`` may be a
+    RaggedPoints of [total, 7] rows (clouds of different sample counts): the packed form travels between the two networks and
+    ``surface_samples_tgt_pred`` comes back as a RaggedPoints."""
     src, tgt, mask = _split(data_dict)
     if deformation_networks.ENCODE_ONCE:
         # the reference's two model() calls (:71, :76) run six encoder passes over two distinct clouds: the source cloud
         # (four times) and the canonicalised surface + target + mask (twice).  Two passes here.
         surf2cano, verts2cano = model.canonicalize([src, data_dict["verts_src"]], src)
         encoding = model.model_deform.encode(model.deform_input(surf2cano, tgt, mask))
-        data_dict["surface_samples_tgt_pred"] = model.model_deform.decode(surf2cano.contiguous(), encoding)
+        data_dict["surface_samples_tgt_pred"] = model.model_deform.decode(
+            surf2cano if isinstance(surf2cano, RaggedPoints) else surf2cano.contiguous(), encoding)
         deformed_verts = model.model_deform.decode(
             verts2cano if isinstance(verts2cano, RaggedPoints) else verts2cano.contiguous(), encoding)
     else:

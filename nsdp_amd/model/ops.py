@@ -102,35 +102,74 @@ def geometry_pyramid(xyz: torch.Tensor, npoints, ks, overlap: bool = True, dims=
         side.wait_stream(main)
     levels = []
     with torch.cuda.stream(side):
-        cur = xyz.detach().contiguous()
-        for n_new, (k_sa, k_blk) in zip(npoints, ks):
-            fps_idx = pu.furthest_point_sample(cur, n_new)
-            new_xyz = pu.gather_rows(cur, fps_idx)
-            sa_idx = pu.knn(new_xyz, cur, k_sa)
-            blk_idx = pu.knn(new_xyz, new_xyz, k_blk) if k_blk is not None else None
-            lv = {"fps_idx": fps_idx, "new_xyz": new_xyz, "sa_idx": sa_idx, "blk_idx": blk_idx}
-            if dims is not None and PYRAMID_LISTS:
-                d = dims[len(levels)]
-                if hip_attention._use_inverse(torch.float32, False, n_new, cur.shape[1], d):
-                    lv["sa_inv"] = hip_attention.inverse_lists(sa_idx, cur.shape[1])
-                if blk_idx is not None and hip_attention._use_inverse(torch.float32, False, n_new, n_new, d):
-                    lv["blk_inv"] = hip_attention.inverse_lists(blk_idx, n_new)
-            levels.append(lv)
-            cur = new_xyz
+        _pyramid_levels(levels, xyz.detach().contiguous(), npoints, ks, dims)
 
     if _GEOMETRY_ABLATE and not torch.cuda.is_current_stream_capturing():
         _ablate_cache[key] = levels
 
+    return levels, _pyramid_join(levels, xyz.device, side if overlap else None)
+
+
+def _pyramid_levels(levels, cur, npoints, ks, dims):
+    """The rectangular levels of the pyramid from the cloud ``cur`` [B,N,3] down, appended to ``levels`` (on the current stream)."""
+    for n_new, (k_sa, k_blk) in zip(npoints, ks):
+        fps_idx = pu.furthest_point_sample(cur, n_new)
+        new_xyz = pu.gather_rows(cur, fps_idx)
+        sa_idx = pu.knn(new_xyz, cur, k_sa)
+        blk_idx = pu.knn(new_xyz, new_xyz, k_blk) if k_blk is not None else None
+        lv = {"fps_idx": fps_idx, "new_xyz": new_xyz, "sa_idx": sa_idx, "blk_idx": blk_idx}
+        if dims is not None and PYRAMID_LISTS:
+            d = dims[len(levels)]
+            if hip_attention._use_inverse(torch.float32, False, n_new, cur.shape[1], d):
+                lv["sa_inv"] = hip_attention.inverse_lists(sa_idx, cur.shape[1])
+            if blk_idx is not None and hip_attention._use_inverse(torch.float32, False, n_new, n_new, d):
+                lv["blk_inv"] = hip_attention.inverse_lists(blk_idx, n_new)
+        levels.append(lv)
+        cur = new_xyz
+
+
+def _pyramid_join(levels, device, side):
     def join():
-        if overlap:
-            torch.cuda.current_stream(xyz.device).wait_stream(side)
+        if side is not None:
+            torch.cuda.current_stream(device).wait_stream(side)
             for lv in levels:
                 for t in lv.values():
                     for u in (t if isinstance(t, tuple) else (t,)):
                         if u is not None:
-                            u.record_stream(torch.cuda.current_stream(xyz.device))
+                            u.record_stream(torch.cuda.current_stream(device))
 
-    return levels, join
+    return join
+
+
+@torch.no_grad()
+def geometry_pyramid_ragged(coords: torch.Tensor, offsets: torch.Tensor, n_max: int, k_begin, npoints, ks, overlap: bool = True):
+    """geometry_pyramid for a packed batch of clouds of different sizes (nsdp_amd.ragged): coords [total,3] (the tight rows),
+    offsets [B+1] int32 on the device, n_max = the largest shape.  Only the first level is ragged: FPS over the packed rows to
+    [B,n1] (packed-row indices), the centres gathered to [B,n1,3], the set abstraction's neighbours searched among each
+    shape's own rows -- and from the centres down the rectangular levels of geometry_pyramid.  Inference only (no inverse
+    lists).  Level 0 comes back in the form its consumers run in, the rows as ONE shape: fps_idx [1,B*n1], new_xyz [1,B*n1,3],
+    sa_idx [1,B*n1,k] index coords[None]; blk_idx [B,n1,k] and the later levels are per shape.  Also returns the first block's
+    self-search ``begin_idx`` [1,total,k_begin] (None: k_begin None), launched on the calling stream: it is needed at once."""
+    B, total = offsets.numel() - 1, coords.shape[0]
+    begin_idx = None
+    if k_begin is not None:
+        begin_idx = pu.knn_ragged_source(coords, coords, offsets, k_begin, n_max, query_offsets=offsets).view(1, total, k_begin)
+    main = torch.cuda.current_stream(coords.device)
+    side = _side_stream(coords.device) if overlap else None
+    if overlap:
+        side.wait_stream(main)
+    levels = []
+    with torch.cuda.stream(side if overlap else main):
+        (n1, *rest), ((k_sa, k_blk), *ks_rest) = npoints, ks
+        fps_idx = pu.furthest_point_sample_ragged(coords, offsets, n1, n_max)                   # [B,n1] packed rows
+        new_xyz = pu.gather_rows(coords.view(1, total, 3), fps_idx.view(1, B * n1))             # [1,B*n1,3]
+        centres = new_xyz.view(B, n1, 3)
+        sa_idx = pu.knn_ragged_source(centres, coords, offsets, k_sa, n_max)                     # [B,n1,k] packed rows
+        blk_idx = pu.knn(centres, centres, k_blk) if k_blk is not None else None
+        levels.append({"fps_idx": fps_idx.view(1, B * n1), "new_xyz": new_xyz, "sa_idx": sa_idx.view(1, B * n1, k_sa),
+                       "blk_idx": blk_idx})
+        _pyramid_levels(levels, centres, rest, ks_rest, None)
+    return begin_idx, levels, _pyramid_join(levels, coords.device, side)
 
 
 class _GatherRows(torch.autograd.Function):

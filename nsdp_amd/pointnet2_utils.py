@@ -76,6 +76,69 @@ def knn_ragged(query: torch.Tensor, offsets: torch.Tensor, source: torch.Tensor,
     return (idx, d2) if (return_dist or dist_out is not None) else idx
 
 
+def _packed_source(what, xyz, offsets, n_max):
+    """The checks the two packed-source calls share (shapes only: the host never reads ``offsets``) -> (cap, B, n_max)."""
+    if xyz.dim() != 2 or xyz.shape[1] != 3:
+        raise _lib.NsdpHipError(f"{what}: the packed cloud must be (cap,3), got {tuple(xyz.shape)}")
+    if offsets.dim() != 1 or offsets.numel() < 2:
+        raise _lib.NsdpHipError(f"{what}: offsets must be (B+1) int32 with B >= 1, got {tuple(offsets.shape)}")
+    cap = int(xyz.shape[0])
+    if cap <= 0 or int(n_max) <= 0:
+        raise _lib.NsdpHipError(f"{what}: an empty packed cloud (cap={cap}, n_max={int(n_max)})")
+    return cap, int(offsets.numel()) - 1, min(int(n_max), cap)
+
+
+def furthest_point_sample_ragged(xyz: torch.Tensor, offsets: torch.Tensor, npoint: int, n_max: int, idx_out=None):
+    """``furthest_point_sample`` over a packed batch of clouds of different sizes (nsdp_amd.ragged): xyz (cap,3), offsets (B+1)
+    int32 on the device, ``n_max`` = an upper bound of any shape's row count (it sizes the workgroup; the kernel clamps to it)
+    -> idx (B,npoint) int32 of PACKED rows (offsets[b] + the index within shape b).  Minus its offset, a shape's row is the
+    result of ``furthest_point_sample`` on that shape alone, ties included, whatever ``n_max`` is.  The host never reads
+    ``offsets``; ``idx_out``: a buffer of the caller's."""
+    with on_device(xyz):
+        cap, B, n_max = _packed_source("furthest_point_sample_ragged", xyz, offsets, n_max)
+        out = torch.empty((B, int(npoint)), dtype=torch.int32, device=xyz.device) if idx_out is None else idx_out
+        if tuple(out.shape) != (B, int(npoint)):
+            raise _lib.NsdpHipError(f"furthest_point_sample_ragged: idx_out must be ({B},{int(npoint)})")
+        tmp = torch.empty((cap,), dtype=torch.float32, device=xyz.device) if n_max > 8192 else None
+        check(lib().nsdp_furthest_point_sampling_ragged(fptr(xyz, "xyz"), iptr(offsets, "offsets"), _c_int(B), _c_int(cap),
+                                                        _c_int(n_max), _c_int(int(npoint)), optptr(tmp), iptr(out, "idx_out"),
+                                                        stream_ptr()), "nsdp_furthest_point_sampling_ragged")
+    return out
+
+
+def knn_ragged_source(query: torch.Tensor, source: torch.Tensor, offsets: torch.Tensor, k: int, n_max: int, query_offsets=None,
+                      return_dist: bool = False, idx_out=None, dist_out=None):
+    """``knn`` against a packed source set: source (cap,3), offsets (B+1) int32 on the device, ``n_max`` as above.  The queries
+    are rectangular (B,n,3) -> idx (B,n,k), or packed themselves, (qcap,3) with ``query_offsets`` (B+1) -> idx (qcap,k); the
+    self-search of a packed cloud is ``knn_ragged_source(xyz, xyz, offsets, k, n_max, query_offsets=offsets)``.  The indices
+    are PACKED rows of ``source``; minus the shape's offset they, and the distance bits, are those of ``knn`` on that shape
+    alone.  Rows of a packed query set at or beyond query_offsets[B] are not written (``idx_out`` / ``dist_out``: buffers of
+    the caller's).  The host never reads either offsets tensor."""
+    with on_device(query):
+        cap, B, n_max = _packed_source("knn_ragged_source", source, offsets, n_max)
+        if query_offsets is None:
+            if query.dim() != 3 or query.shape[2] != 3 or query.shape[0] != B:
+                raise _lib.NsdpHipError(f"knn_ragged_source: rectangular queries must be ({B},n,3), got {tuple(query.shape)}")
+            n, qcap, lead = int(query.shape[1]), 0, (B, int(query.shape[1]))
+        else:
+            if query.dim() != 2 or query.shape[1] != 3 or query_offsets.numel() != B + 1:
+                raise _lib.NsdpHipError(f"knn_ragged_source: packed queries must be (qcap,3) with {B + 1} offsets, got "
+                                        f"{tuple(query.shape)}, {query_offsets.numel()}")
+            n, qcap, lead = 0, int(query.shape[0]), (int(query.shape[0]),)
+        want = lead + (int(k),)
+        idx = torch.empty(want, dtype=torch.int32, device=query.device) if idx_out is None else idx_out
+        d2 = dist_out if dist_out is not None else (
+            torch.empty(want, dtype=torch.float32, device=query.device) if return_dist else None)
+        if tuple(idx.shape) != want or (d2 is not None and tuple(d2.shape) != want):
+            raise _lib.NsdpHipError(f"knn_ragged_source: output buffers must be {want}")
+        check(lib().nsdp_knn_ragged_source(fptr(query, "query"), optptr(None) if query_offsets is None else iptr(query_offsets, "query_offsets"),
+                                           fptr(source, "source"), iptr(offsets, "offsets"), _c_int(B), _c_int(n), _c_int(qcap),
+                                           _c_int(cap), _c_int(n_max), _c_int(int(k)), iptr(idx, "idx_out"),
+                                           optptr(None) if d2 is None else fptr(d2, "dist_out"), stream_ptr()),
+              "nsdp_knn_ragged_source")
+    return (idx, d2) if (return_dist or dist_out is not None) else idx
+
+
 def gather_rows(points: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
     """index_points for a 2-D index: points (B,N,C), idx (B,S) int32 -> (B,S,C)."""
     B, N, C = points.shape

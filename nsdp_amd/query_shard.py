@@ -159,6 +159,8 @@ def _refuse_ragged(data_dict):
     if isinstance(data_dict.get("verts_src"), RaggedPoints):
         raise NotImplementedError("query_sharded: splitting a ragged (packed) vertex set over ranks is not implemented -- "
                                   "decode it on one GPU (ragged.RaggedTestOnBatch) or pad the batch to a [B, max, 3] tensor")
+    if any(isinstance(data_dict.get(k), RaggedPoints) for k in ("surface_samples_inputs", "surface_samples_src")):
+        raise NotImplementedError("query_sharded: ragged (packed) surface clouds are not split over ranks -- run the step on one GPU")
 
 
 class QueryShardedTestOnBatch:

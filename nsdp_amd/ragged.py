@@ -11,8 +11,23 @@ Rows at or beyond ``total`` are padding: no kernel reads them as results or writ
 ``B`` from the host (they fix the launch grid) and everything else from ``offsets`` on the device, so ONE captured graph
 serves every batch of ``B`` meshes whose vertices sum to at most the capacity (``RaggedTestOnBatch(graph=True)``).  A
 decoder wave's 16 queries and a kNN workgroup's 256 belong to one shape and a shape's last tile is partial, exactly like
-the tail of the rectangular call: every row gets the bits the rectangular call gives it.  The surface cloud stays
-rectangular ([B, NS, 7]: the encoder, its BatchNorm and the data contract sample a fixed count).  Inference only.
+the tail of the rectangular call: every row gets the bits the rectangular call gives it.  Inference only.
+
+The surface cloud may be packed as well -- shapes that bring different numbers of surface samples (every vertex of a mesh as
+the user-handle data does, a partial scan), which cannot be padded: extra points change the sampling, every neighbourhood and
+the max-pool.
+
+    surf = RaggedPoints.from_rows([s0, s1, s2])                     # [n_b, 7] rows: source, target, handle mask
+    data_dict["surface_samples_inputs"] = surf
+    data_dict["surface_samples_src"] = surf.columns(0, 3)
+    loss, data_dict = test_on_batch(model, data_dict, config)       # surface_samples_tgt_pred comes back packed as well
+
+Only the encoder's first level is ragged (PointTransformerEncoder.forward): farthest-point sampling and the neighbour searches
+run over the packed rows (pointnet2_utils.furthest_point_sample_ragged / knn_ragged_source, sizes from the offsets on the
+device), the first attention block and the first set abstraction see the rows as one shape [1, total, .], and from the first
+down-sampled level on every tensor is [B, n1, .] again.  With eval-mode BatchNorm (a per-row affine map) every shape gets what
+its own batch-1 call gives it.  The encoder works on the tight rows ``packed[:total]``, so a call with ragged surfaces reads
+the counts on the host and is not captured into a graph (RaggedTestOnBatch runs it eagerly).
 """
 from __future__ import annotations
 
@@ -60,6 +75,41 @@ class RaggedPoints:
         if total:
             torch.cat(tensors, dim=0, out=packed[:total])
         return cls(packed, offsets_of(counts, packed.device), counts)
+
+    @classmethod
+    def from_rows(cls, tensors, capacity=None):
+        """``from_list`` for rows of any one width: [n_b, C] tensors (a surface cloud's [n_b, 7] rows) -> packed [capacity, C]."""
+        tensors = list(tensors)
+        if not tensors:
+            raise ValueError("RaggedPoints.from_rows: no shapes")
+        for t in tensors:
+            if not torch.is_tensor(t) or t.dim() != 2 or t.shape[1] != tensors[0].shape[1] or t.shape[1] < 1:
+                raise ValueError(f"RaggedPoints.from_rows: every shape must be [n, C] with one C, got {tuple(getattr(t, 'shape', ()))}")
+            if t.device != tensors[0].device or t.dtype != tensors[0].dtype:
+                raise ValueError("RaggedPoints.from_rows: the shapes must share a device and a dtype")
+        counts = [int(t.shape[0]) for t in tensors]
+        total = sum(counts)
+        capacity = total if capacity is None else int(capacity)
+        if total > capacity:
+            raise ValueError(f"RaggedPoints.from_rows: {total} rows do not fit the capacity {capacity}")
+        packed = tensors[0].new_zeros((capacity, int(tensors[0].shape[1])))
+        if total:
+            torch.cat(tensors, dim=0, out=packed[:total])
+        return cls(packed, offsets_of(counts, packed.device), counts)
+
+    def columns(self, lo: int, hi: int) -> "RaggedPoints":
+        """Columns [lo, hi) of every row as a packed set of their own (a contiguous copy) over the same offsets and counts:
+        the coordinates ``columns(0, 3)`` of a [capacity, 7] surface input."""
+        lo, hi = int(lo), int(hi)
+        if not 0 <= lo < hi <= self.packed.shape[1]:
+            raise ValueError(f"RaggedPoints.columns: [{lo}, {hi}) of {self.packed.shape[1]} columns")
+        return RaggedPoints(self.packed[:, lo:hi].contiguous(), self.offsets, self._counts)
+
+    def same_layout(self, other) -> bool:
+        """Do the two sets describe the same shapes in the same rows (one offsets tensor, or equal host counts)?"""
+        if not isinstance(other, RaggedPoints) or other.batch != self.batch or other.capacity != self.capacity:
+            return False
+        return other.offsets is self.offsets or other.counts == self.counts
 
     @property
     def capacity(self) -> int:
@@ -169,7 +219,10 @@ class RaggedTestOnBatch:
     mode and its weights must not change afterwards) over a static [capacity, 3] vertex buffer, static offsets and static
     copies of the rectangular inputs.  Every later call with the same model, B and surface shapes and ``total <= capacity``
     copies its vertices and offsets into them and replays (``replays``) -- whatever the mix of sizes: the kernels read the
-    sizes from the offsets on the device.  Anything else runs eagerly (``eager_calls``)."""
+    sizes from the offsets on the device.  Anything else runs eagerly (``eager_calls``) -- a call whose SURFACE clouds are
+    ragged (``surface_samples_inputs`` / ``surface_samples_src`` as RaggedPoints: passed through as they are, and
+    ``surface_samples_tgt_pred`` comes back as one) among them: the encoder works on the tight rows of the cloud, whose number
+    the host reads, so such a step is not captured."""
 
     RECT_INPUTS = ("surface_samples_inputs", "surface_samples_src")
 
@@ -220,7 +273,8 @@ class RaggedTestOnBatch:
     def __call__(self, model, data_dict, config, compute_loss=False):
         verts = as_ragged(data_dict["verts_src"])
         counts, total = verts.counts, verts.total
-        out = self._replayed(model, data_dict, verts, config) if self.graph else None
+        ragged_surface = any(isinstance(data_dict.get(k), RaggedPoints) for k in self.RECT_INPUTS)
+        out = self._replayed(model, data_dict, verts, config) if (self.graph and not ragged_surface) else None
         if out is None:
             self.eager_calls += 1
             tight = verts if verts.capacity == total else RaggedPoints(verts.packed[:total].contiguous(), verts.offsets, counts)
