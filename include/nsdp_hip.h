@@ -13,7 +13,12 @@
  *     mirroring `at::cuda::getCurrentCUDAStream()` (e.g. sampling_gpu.cu:180);
  *   - return value: 0 on success, a negative NSDP_E* code for bad arguments, or a positive hipError_t.
  *     Nothing ever calls exit() (the reference does on a launch failure, cuda_utils.h:30-39);
- *   - re-entrant, no global state besides a thread-local last-error string.
+ *   - re-entrant, no global state besides a thread-local last-error string;
+ *   - memory: outputs and workspaces may be UNINITIALISED on entry (an output is read only where the text says it is accumulated
+ *     into -- `accumulate != 0`, running statistics, counters --, a workspace only where the same call wrote it); a call touches
+ *     exactly the declared bytes -- its outputs as shaped here (rows a packed set leaves alone stay as they were) and the first
+ *     `*_workspace_bytes` / `*_bytes` / `*_floats` bytes of a scratch or pack buffer, whose padding the pack kernels write as
+ *     zeros; inputs are never written.  tests/test_poisoned_arena_gpu.py holds every entry to this.
  */
 #ifndef NSDP_HIP_H_
 #define NSDP_HIP_H_
@@ -286,7 +291,8 @@ int nsdp_linear_bf16x3_addend_f32(const float *X, const void *Wp, const float *b
 /* Position-encoding MLP fc_delta = Linear(3, K) -> ReLU -> Linear(K, N) (reference model/encoder/blocks.py:86-90, :281-285,
  * model/decoder/blocks.py:30-34) straight from the coordinates: Y[M,N] = relu(X4 W0^T + b0) W^T + bias.  The hidden tensor [M, K]
  * is neither written nor read: the GEMM's operand producer evaluates the K = 4 layer for the 16-byte rows X4 [M,4] (zero-padded
- * coordinates) with the expression of nsdp_linear_f32's K = 4 kernel -- the values are bit for bit those of the two-launch form.
+ * coordinates) with the expression of nsdp_linear_f32's K = 4 kernel -- the values are bit for bit those of the two-launch form
+ * wherever nsdp_linear_f32 takes that kernel (M >= 4096; with fewer rows its general kernel rounds the four products otherwise).
  * W0 [K,4] row-major zero-padded, b0 [K] or NULL, Wp = nsdp_pack_weight_bf16x3 of W [N,K].  gk != NULL: the gathered addend of
  * nsdp_linear_bf16x3_gather_f32 joins in the epilogue (gq == NULL: its one-table form).  Shapes: nsdp_linear_bf16x3_h0_supported. */
 int nsdp_linear_bf16x3_h0_supported(long long M, int N, int K);
