@@ -39,6 +39,16 @@ exact alternative; interleaved repetitions, median, as above) and ``l2_vs_per_sh
 distance between the two vertex predictions: reported, not asserted -- the dense layers pick tile shapes from the row count, so
 the two are close, not bit-equal).  ``--out DIR``: surface_samples_tgt_pred.npy is the packed [total, 3] array with
 surface_offsets.npy; verts_tgt_pred.npy is packed with verts_offsets.npy under ``--vertex-counts``, else [B, NQ, 3].
+
+    python -m nsdp_amd.infer CONFIG [--vertex-counts ...|--batch B] --metrics [P]
+
+The evaluation metrics of the whole batch of predicted meshes in one call (eval_metric.compute_evaluation_metrics_batch, P
+surface points per mesh, default 30000; rank 0, after the timed region).  The synthetic meshes get synthetic faces -- triples of
+distinct vertices, no degenerate triangle -- and targets = the prediction plus a small deterministic offset.  The line gains
+``metrics`` ({'l2', 'fnc', 'cd'}, a list per shape), ``metrics_points``, ``metrics_ms_batch`` (one call and its one read-back),
+``metrics_ms_per_mesh_loop`` (eval_metric.compute_evaluation_metrics mesh after mesh, its three read-backs per mesh included;
+both wall-clock, interleaved repetitions, median) and ``metrics_l2_fnc_max_abs_diff`` (batch against loop; ``cd`` uses
+different draws and is not compared).
 """
 from __future__ import annotations
 
@@ -91,9 +101,75 @@ def build_parser():
                     help="rows of the packed vertex buffer (default: the sum of --vertex-counts); a captured graph serves every "
                          "batch of as many shapes whose vertices sum to at most this")
     ap.add_argument("--reps", type=int, default=5, help="--vertex-counts: interleaved repetitions of the comparison timings")
+    ap.add_argument("--metrics", type=int, nargs="?", const=30000, default=None, metavar="P",
+                    help="evaluation metrics of the predicted batch in one call, P surface points per mesh (default 30000), "
+                         "timed against the per-mesh loop")
     ap.add_argument("--decoder-dtype", default=None, choices=["f32", "bf16"],
                     help="operand type of the fused decoder kernel on every rank (default: NSDP_FUSED_DECODER_DTYPE, else f32)")
     return ap
+
+
+def _synthetic_faces(n: int):
+    """Faces for a synthetic mesh of n >= 3 vertices: (i, i+1, i+2) and, from 8 vertices on, (i, i+3, i+7), indices mod n --
+    three distinct vertices each."""
+    import torch
+    i = torch.arange(n, dtype=torch.int32)
+    faces = [torch.stack((i, (i + 1) % n, (i + 2) % n), dim=1)]
+    if n >= 8:
+        faces.append(torch.stack((i, (i + 3) % n, (i + 7) % n), dim=1))
+    return torch.cat(faces)
+
+
+def _metrics(args, pred):
+    """The --metrics keys for the predicted vertices (a RaggedPoints or [B, V, 3]): the batch call, then the per-mesh loop."""
+    import statistics
+    import time
+    import torch
+    from . import eval_metric
+    from .ragged import RaggedPoints
+    P = int(args.metrics)
+    ragged = isinstance(pred, RaggedPoints)
+    rows = [r.contiguous() for r in pred.split()] if ragged else [pred[b] for b in range(pred.shape[0])]
+    if min(int(r.shape[0]) for r in rows) < 3:
+        sys.exit("nsdp_amd.infer: --metrics needs at least 3 vertices in every mesh")
+    dev = rows[0].device
+    faces = [_synthetic_faces(int(r.shape[0])).to(dev) for r in rows]
+    shift = [0.01 * torch.sin(0.37 * torch.arange(int(r.shape[0]), device=dev, dtype=torch.float32)[:, None]
+                              + torch.arange(3, device=dev, dtype=torch.float32)) for r in rows]
+    tgts = [r + d for r, d in zip(rows, shift)]
+    if ragged:
+        batch = {"verts_tgt_pred": RaggedPoints.from_list(rows), "verts_tgt": RaggedPoints.from_list(tgts),
+                 "faces": RaggedPoints.from_rows(faces)}
+    else:
+        batch = {"verts_tgt_pred": torch.stack(rows), "verts_tgt": torch.stack(tgts), "faces": torch.stack(faces)}
+    singles = [{"verts_tgt_pred": r[None], "verts_tgt": t[None], "faces": f[None]} for r, t, f in zip(rows, tgts, faces)]
+    gen = torch.Generator(device=dev).manual_seed(SEED_DATA)
+
+    def run_batch():
+        m = eval_metric.compute_evaluation_metrics_batch(batch, pointcloud_size=P, generator=gen)
+        return {k: v.tolist() for k, v in m.items()}
+
+    def run_loop():
+        per = [eval_metric.compute_evaluation_metrics(one, pointcloud_size=P, generator=gen) for one in singles]
+        return {k: [m[k] for m in per] for k in ("l2", "fnc", "cd")}
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3
+
+    got, loop = run_batch(), run_loop()                                  # (warm-up of both, and the comparison)
+    reps = {"metrics_ms_batch": [], "metrics_ms_per_mesh_loop": []}
+    for _ in range(max(1, args.reps)):
+        reps["metrics_ms_batch"].append(timed(run_batch))
+        reps["metrics_ms_per_mesh_loop"].append(timed(run_loop))
+    diff = max(abs(a - b) for k in ("l2", "fnc") for a, b in zip(got[k], loop[k]))
+    return {"metrics": got, "metrics_points": P,
+            **{k: round(statistics.median(v), 4) for k, v in reps.items()},
+            **{k + "_reps": [round(x, 4) for x in v] for k, v in reps.items()},
+            "metrics_l2_fnc_max_abs_diff": diff}
 
 
 def _ragged(args, config, model, test_fn, dd, counts, ns):
@@ -166,6 +242,8 @@ def _ragged(args, config, model, test_fn, dd, counts, ns):
             **{k: round(statistics.median(v), 4) for k, v in reps.items()},
             **{k + "_reps": [round(x, 4) for x in v] for k, v in reps.items()},
             "equal_to_padded": bool(equal)}
+    if args.metrics is not None:
+        line.update(_metrics(args, rdd["verts_tgt_pred"].like(pred["verts_tgt_pred"])))
     print(json.dumps(line), flush=True)
     step.close()
     padded.close()
@@ -237,6 +315,8 @@ def _ragged_surface(args, config, model, test_fn, dd, scounts, vcounts):
             **{k: round(statistics.median(v), 4) for k, v in reps.items()},
             **{k + "_reps": [round(x, 4) for x in v] for k, v in reps.items()},
             "l2_vs_per_shape_loop": l2}
+    if args.metrics is not None:
+        line.update(_metrics(args, pred))
     print(json.dumps(line), flush=True)
     return 0
 
@@ -283,6 +363,10 @@ def main(argv=None):
         if scounts and len(scounts) != len(counts):
             sys.exit(f"nsdp_amd.infer: {len(scounts)} surface counts against {len(counts)} vertex counts")
     world = int(os.environ.get("WORLD_SIZE", "1"))
+    if args.metrics is not None and args.metrics < 1:
+        sys.exit(f"nsdp_amd.infer: --metrics wants a positive number of surface points, got {args.metrics}")
+    if args.metrics is not None and counts and min(counts) < 3:
+        sys.exit("nsdp_amd.infer: --metrics needs at least 3 vertices in every mesh of --vertex-counts")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         from .train import launch_ranks
         return launch_ranks(args.gpus, argv, module="nsdp_amd.infer")
@@ -394,6 +478,8 @@ def main(argv=None):
                 "ranks_share_a_device": len({(r["pci_domain_id"], r["pci_bus_id"]) for r in ranks}) < world,
                 "ranks": [{k: r[k] for k in ("rank", "device_index", "pci_domain_id", "pci_bus_id", "hip_visible_devices",
                                              "ms_per_call", "replays", "eager_calls")} for r in ranks]}
+        if args.metrics is not None:
+            line.update(_metrics(args, dd["verts_tgt_pred"]))
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.destroy_process_group()

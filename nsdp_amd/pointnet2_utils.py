@@ -139,6 +139,63 @@ def knn_ragged_source(query: torch.Tensor, source: torch.Tensor, offsets: torch.
     return (idx, d2) if (return_dist or dist_out is not None) else idx
 
 
+def nn_dist2(query: torch.Tensor, source: torch.Tensor, return_index: bool = False):
+    """The squared distance of every query point to its nearest source point (include/nsdp_eval.h): query (B,n,3), source
+    (B,m,3) -> dist2 (B,n) fp32 with the bits of ``knn(query, source, 1, return_dist=True)``, and with ``return_index`` that
+    search's index (B,n) int32 as well.  Without the index the source range is split over workgroups (the metric's case)."""
+    with on_device(query):
+        if query.dim() != 3 or query.shape[2] != 3 or source.dim() != 3 or source.shape[2] != 3 or source.shape[0] != query.shape[0]:
+            raise _lib.NsdpHipError(f"nn_dist2: query (B,n,3) and source (B,m,3), got {tuple(query.shape)}, {tuple(source.shape)}")
+        B, n, m = int(query.shape[0]), int(query.shape[1]), int(source.shape[1])
+        d2 = torch.empty((B, n), dtype=torch.float32, device=query.device)
+        idx = torch.empty((B, n), dtype=torch.int32, device=query.device) if return_index else None
+        check(lib().nsdp_nn_dist2(fptr(query, "query"), fptr(source, "source"), _c_int(B), _c_int(n), _c_int(m), fptr(d2, "dist2_out"),
+                                  optptr(idx), stream_ptr()), "nsdp_nn_dist2")
+    return (d2, idx) if return_index else d2
+
+
+def nn_dist2_ragged(query: torch.Tensor, query_offsets: torch.Tensor, source: torch.Tensor, source_offsets: torch.Tensor,
+                    return_index: bool = False, dist_out=None, idx_out=None):
+    """``nn_dist2`` with both sets packed (nsdp_amd.ragged): query (qcap,3) + query_offsets (B+1), source (scap,3) +
+    source_offsets (B+1), int32 offsets on the device -> dist2 (qcap) and, with ``return_index``, the PACKED source row (qcap)
+    int32: element for element ``knn_ragged_source`` at k = 1.  Rows at or beyond query_offsets[B] are not written
+    (``dist_out`` / ``idx_out``: buffers of the caller's); a shape without source rows gets FLT_MAX.  The host never reads
+    either offsets tensor."""
+    with on_device(query):
+        if query.dim() != 2 or query.shape[1] != 3 or source.dim() != 2 or source.shape[1] != 3:
+            raise _lib.NsdpHipError(f"nn_dist2_ragged: packed query (qcap,3) and source (scap,3), got {tuple(query.shape)}, "
+                                    f"{tuple(source.shape)}")
+        if query_offsets.dim() != 1 or query_offsets.numel() < 2 or source_offsets.shape != query_offsets.shape:
+            raise _lib.NsdpHipError(f"nn_dist2_ragged: both offsets must be (B+1) int32 with B >= 1, got {tuple(query_offsets.shape)}, "
+                                    f"{tuple(source_offsets.shape)}")
+        B, qcap, scap = int(query_offsets.numel()) - 1, int(query.shape[0]), int(source.shape[0])
+        d2 = torch.empty((qcap,), dtype=torch.float32, device=query.device) if dist_out is None else dist_out
+        idx = idx_out if idx_out is not None else (
+            torch.empty((qcap,), dtype=torch.int32, device=query.device) if return_index else None)
+        if tuple(d2.shape) != (qcap,) or (idx is not None and tuple(idx.shape) != (qcap,)):
+            raise _lib.NsdpHipError(f"nn_dist2_ragged: output buffers must be ({qcap},)")
+        check(lib().nsdp_nn_dist2_ragged(fptr(query, "query"), iptr(query_offsets, "query_offsets"), fptr(source, "source"),
+                                         iptr(source_offsets, "source_offsets"), _c_int(B), _c_int(qcap), _c_int(scap),
+                                         fptr(d2, "dist_out"), optptr(None) if idx is None else iptr(idx, "idx_out"),
+                                         stream_ptr()), "nsdp_nn_dist2_ragged")
+    return (d2, idx) if (return_index or idx_out is not None) else d2
+
+
+def segment_mean(values: torch.Tensor, offsets: torch.Tensor, sqrt: bool = False) -> torch.Tensor:
+    """Per-shape mean of a packed column (include/nsdp_eval.h): values (cap) fp32, offsets (B+1) int32 on the device -> (B)
+    fp32, the mean of v -- or of sqrt(max(v, 0)) with ``sqrt`` -- over each shape's rows, accumulated in double in a fixed
+    order: the bits depend on that shape's rows alone.  NaN for a shape without rows.  No host synchronisation."""
+    with on_device(values):
+        if values.dim() != 1 or offsets.dim() != 1 or offsets.numel() < 2:
+            raise _lib.NsdpHipError(f"segment_mean: values (cap) and offsets (B+1) with B >= 1, got {tuple(values.shape)}, "
+                                    f"{tuple(offsets.shape)}")
+        B = int(offsets.numel()) - 1
+        out = torch.empty((B,), dtype=torch.float32, device=values.device)
+        check(lib().nsdp_segment_mean_f32(fptr(values, "values"), iptr(offsets, "offsets"), _c_int(B), _c_int(int(values.shape[0])),
+                                          _c_int(1 if sqrt else 0), fptr(out, "out"), stream_ptr()), "nsdp_segment_mean_f32")
+    return out
+
+
 def gather_rows(points: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
     """index_points for a 2-D index: points (B,N,C), idx (B,S) int32 -> (B,S,C)."""
     B, N, C = points.shape
