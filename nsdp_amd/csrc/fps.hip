@@ -20,6 +20,7 @@
 #include <cmath>
 
 #include "common.h"
+#include "fps_common.h"
 #include "prof.h"
 #include "ragged.h"
 
@@ -27,61 +28,7 @@
 
 namespace {
 
-constexpr int kRankShift = 22;  // low bits: k div BS, high bits: bit-reversed (k mod BS)
-
-template <int CTRL>
-__device__ __forceinline__ long long dpp_max_step(long long v) {
-  const int lo = __builtin_amdgcn_update_dpp(0, static_cast<int>(v), CTRL, 0xf, 0xf, false);
-  const int hi = __builtin_amdgcn_update_dpp(0, static_cast<int>(v >> 32), CTRL, 0xf, 0xf, false);
-  const long long o = (static_cast<long long>(hi) << 32) | static_cast<unsigned>(lo);
-  return o > v ? o : v;
-}
-
-// max over the 64 lanes of a wave, result in every lane.
-__device__ __forceinline__ long long wave_max_i64(long long v) {
-  v = dpp_max_step<0xB1>(v);   // quad_perm [1,0,3,2]
-  v = dpp_max_step<0x4E>(v);   // quad_perm [2,3,0,1]
-  v = dpp_max_step<0x141>(v);  // row_half_mirror
-  v = dpp_max_step<0x140>(v);  // row_mirror  -> every lane of a 16-lane row holds the row max
-  {
-    const unsigned lo = static_cast<unsigned>(v), hi = static_cast<unsigned>(v >> 32);
-    const auto l = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
-    const auto h = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
-    const long long a = (static_cast<long long>(h[0]) << 32) | l[0];
-    const long long b = (static_cast<long long>(h[1]) << 32) | l[1];
-    v = a > b ? a : b;
-  }
-  {
-    const unsigned lo = static_cast<unsigned>(v), hi = static_cast<unsigned>(v >> 32);
-    const auto l = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
-    const auto h = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
-    const long long a = (static_cast<long long>(h[0]) << 32) | l[0];
-    const long long b = (static_cast<long long>(h[1]) << 32) | l[1];
-    v = a > b ? a : b;
-  }
-  return v;
-}
-
-__device__ __forceinline__ unsigned tie_priority(int k, int BS, int log2BS) {
-  const unsigned kmod = static_cast<unsigned>(k) & static_cast<unsigned>(BS - 1);
-  const unsigned br = log2BS ? (__brev(kmod) >> (32 - log2BS)) : 0u;
-  const unsigned rank = (br << kRankShift) | (static_cast<unsigned>(k) >> log2BS);
-  return ~rank;  // larger = preferred on a tie
-}
-
-__device__ __forceinline__ int decode_winner(long long key, int log2BS) {
-  if (key < 0) return 0;  // no valid point at all: reference keeps besti = 0
-  const unsigned rank = ~static_cast<unsigned>(key);
-  const unsigned br = rank >> kRankShift;
-  const unsigned q = rank & ((1u << kRankShift) - 1u);
-  const unsigned kmod = log2BS ? (__brev(br) >> (32 - log2BS)) : 0u;
-  return static_cast<int>((q << log2BS) | kmod);
-}
-
-__device__ __forceinline__ bool point_valid(float x, float y, float z) {
-  const float mag = (x * x) + (y * y) + (z * z);  // contraction is off in this file
-  return !(static_cast<double>(mag) <= 1e-3);     // sampling_gpu.cu:100-101 (float vs double literal)
-}
+using namespace nsdp::fps;  // fps_common.h: the key, the maxima and the shape of a packed cloud
 
 // Register-resident FPS of one cloud by one workgroup: T threads, P points per thread (N <= T*P).  The indices written are
 // `base` + the index within the cloud (0 for a rectangular batch, the shape's first row for a packed one).
@@ -98,17 +45,8 @@ __device__ __forceinline__ void fps_reg_body(char *smem, const float *__restrict
 #pragma unroll
   for (int s = 0; s < P; ++s) {
     const int k = tid + s * T;
-    if (k < N) {
-      const float x = xyz[k * 3 + 0], y = xyz[k * 3 + 1], z = xyz[k * 3 + 2];
-      px[s] = x; py[s] = y; pz[s] = z;
-      pt[s] = point_valid(x, y, z) ? 1e10f : -1.0f;  // invalid points never win and never update
-      prio[s] = tie_priority(k, BS, log2BS);
-      if (LDS_XYZ) sxyz[k] = make_float4(x, y, z, 0.f);
-    } else {
-      px[s] = py[s] = pz[s] = 0.f;
-      pt[s] = -1.0f;
-      prio[s] = 0u;
-    }
+    init_point(xyz, k, N, BS, log2BS, px[s], py[s], pz[s], pt[s], prio[s]);
+    if (LDS_XYZ && k < N) sxyz[k] = make_float4(px[s], py[s], pz[s], 0.f);
   }
   if (tid == 0) out[0] = base;
   if (LDS_XYZ) __syncthreads();
@@ -122,28 +60,8 @@ __device__ __forceinline__ void fps_reg_body(char *smem, const float *__restrict
   }
 
   for (int j = 1; j < M; ++j) {
-    long long best = LLONG_MIN;
-#pragma unroll
-    for (int s = 0; s < P; ++s) {
-      const float d = nsdp::sq_dist3(px[s], py[s], pz[s], cx, cy, cz);
-      const float t = fminf(d, pt[s]);
-      pt[s] = t;
-      const long long key = (static_cast<long long>(__float_as_int(t)) << 32) | prio[s];
-      best = key > best ? key : best;
-    }
-    best = wave_max_i64(best);
-    if (W > 1) {
-      long long *slot = slots + (j & 1) * W;
-      if ((tid & 63) == 0) slot[tid >> 6] = best;
-      __syncthreads();
-      long long g = slot[0];
-#pragma unroll
-      for (int w = 1; w < W; ++w) {
-        const long long o = slot[w];
-        g = o > g ? o : g;
-      }
-      best = g;
-    }
+    long long best = wave_max_i64(update_points<P>(px, py, pz, pt, prio, cx, cy, cz));
+    if (W > 1) best = block_max_i64<W>(slots, j, tid, best);
     const int old = decode_winner(best, log2BS);
     if (LDS_XYZ) {
       const float4 c = sxyz[old];
@@ -164,25 +82,6 @@ __global__ __launch_bounds__(T) void fps_reg_kernel(const float *__restrict__ xy
                               idx_all + static_cast<size_t>(blockIdx.x) * M, 0);
 }
 
-// One cloud of a packed set (ragged.h): its rows, its size and its tie-rule block size BS = min(512, 2^floor(log2 n)) -- the
-// reference's opt_n_threads by integer arithmetic -- all from the offsets on the device.  `n_max` (the host's bound: it sized
-// the workgroup and the LDS copy) caps the row count on top of the offsets' clamp.  false: the shape has no rows; every slot of
-// its output then holds its (clamped) first-row index.
-__device__ __forceinline__ bool fps_ragged_shape(const int32_t *__restrict__ offsets, int cap, int n_max, int M,
-                                                 int32_t *__restrict__ out, int &lo, int &N, int &BS, int &log2BS) {
-  int hi;
-  nsdp::ragged_range(offsets, static_cast<int>(blockIdx.x), cap, lo, hi);
-  N = min(hi - lo, n_max);
-  if (N <= 0) {
-    const int fill = min(lo, cap - 1);
-    for (int j = threadIdx.x; j < M; j += blockDim.x) out[j] = fill;
-    return false;
-  }
-  log2BS = min(9, 31 - __builtin_clz(static_cast<unsigned>(N)));
-  BS = 1 << log2BS;
-  return true;
-}
-
 template <int T, int P, bool LDS_XYZ>
 __global__ __launch_bounds__(T) void fps_reg_ragged_kernel(const float *__restrict__ xyz_packed,
                                                            const int32_t *__restrict__ offsets, int cap, int n_max, int M,
@@ -190,7 +89,7 @@ __global__ __launch_bounds__(T) void fps_reg_ragged_kernel(const float *__restri
   extern __shared__ __attribute__((aligned(16))) char smem[];
   int32_t *out = idx_all + static_cast<size_t>(blockIdx.x) * M;
   int lo, N, BS, log2BS;
-  if (!fps_ragged_shape(offsets, cap, min(n_max, T * P), M, out, lo, N, BS, log2BS)) return;   // (uniform: before any barrier)
+  if (!fps_ragged_shape(offsets, static_cast<int>(blockIdx.x), cap, min(n_max, T * P), M, out, lo, N, BS, log2BS)) return;   // (uniform: before any barrier)
   fps_reg_body<T, P, LDS_XYZ>(smem, xyz_packed + static_cast<size_t>(lo) * 3, N, M, BS, log2BS, out, lo);
 }
 
@@ -215,16 +114,7 @@ __device__ __forceinline__ void fps_big_body(const float *__restrict__ xyz, floa
           (static_cast<long long>(__float_as_int(t)) << 32) | tie_priority(k, BS, log2BS);
       best = key > best ? key : best;
     }
-    best = wave_max_i64(best);
-    long long *slot = slots + (j & 1) * W;
-    if ((tid & 63) == 0) slot[tid >> 6] = best;
-    __syncthreads();
-    long long g = slot[0];
-#pragma unroll
-    for (int w = 1; w < W; ++w) {
-      const long long o = slot[w];
-      g = o > g ? o : g;
-    }
+    const long long g = block_max_i64<W>(slots, j, tid, wave_max_i64(best));
     const int old = decode_winner(g, log2BS);
     cx = xyz[old * 3 + 0]; cy = xyz[old * 3 + 1]; cz = xyz[old * 3 + 2];
     if (tid == 0) out[j] = base + old;
@@ -246,17 +136,8 @@ __global__ __launch_bounds__(T) void fps_big_ragged_kernel(const float *__restri
                                                            int n_max, int M, int32_t *__restrict__ idx_all) {
   int32_t *out = idx_all + static_cast<size_t>(blockIdx.x) * M;
   int lo, N, BS, log2BS;
-  if (!fps_ragged_shape(offsets, cap, n_max, M, out, lo, N, BS, log2BS)) return;
+  if (!fps_ragged_shape(offsets, static_cast<int>(blockIdx.x), cap, n_max, M, out, lo, N, BS, log2BS)) return;
   fps_big_body<T>(xyz_packed + static_cast<size_t>(lo) * 3, tmp + lo, N, M, BS, log2BS, out, lo);
-}
-
-// cuda_utils.h:15-19 -- same double arithmetic as the reference host code.
-int opt_n_threads(int work_size) {
-  const int pow_2 = static_cast<int>(std::log(static_cast<double>(work_size)) / std::log(2.0));
-  int t = 1 << pow_2;
-  if (t > 512) t = 512;
-  if (t < 1) t = 1;
-  return t;
 }
 
 template <int T, int P, bool LDS_XYZ>

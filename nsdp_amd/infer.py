@@ -177,7 +177,7 @@ def _ragged(args, config, model, test_fn, dd, counts, ns):
     import statistics
     import numpy as np
     import torch
-    from . import hip_decoder
+    from . import hip_decoder, pointnet2_utils
     from .query_shard import QueryShards, query_sharded
     from .ragged import RaggedPoints, RaggedTestOnBatch
     B, total = len(counts), sum(counts)
@@ -228,6 +228,7 @@ def _ragged(args, config, model, test_fn, dd, counts, ns):
         reps["ms_ragged"].append(timed(run_ragged, args.steps))
         reps["ms_padded"].append(timed(run_padded, args.steps))
         reps["ms_per_shape_loop"].append(timed(run_loop, args.steps))
+    pointnet2_utils.check_fps_cluster()      # (a large surface cloud is sampled by a workgroup cluster: no wait may have given up)
     if args.out:
         os.makedirs(args.out, exist_ok=True)
         for k in KEYS:
@@ -255,7 +256,7 @@ def _ragged_surface(args, config, model, test_fn, dd, scounts, vcounts):
     import statistics
     import numpy as np
     import torch
-    from . import hip_decoder
+    from . import hip_decoder, pointnet2_utils
     from .ragged import RaggedPoints
     B = len(scounts)
     surf = RaggedPoints.from_rows([dd["surface_samples_inputs"][b, :n] for b, n in enumerate(scounts)])
@@ -298,6 +299,7 @@ def _ragged_surface(args, config, model, test_fn, dd, scounts, vcounts):
     for _ in range(max(1, args.reps)):
         reps["ms_ragged"].append(timed(run_ragged, args.steps))
         reps["ms_per_shape_loop"].append(timed(run_loop, args.steps))
+    pointnet2_utils.check_fps_cluster()      # (a large surface cloud is sampled by a workgroup cluster: no wait may have given up)
     if args.out:
         os.makedirs(args.out, exist_ok=True)
         np.save(os.path.join(args.out, "surface_samples_tgt_pred.npy"), rdd["surface_samples_tgt_pred"].packed.cpu().numpy())
@@ -396,7 +398,7 @@ def main(argv=None):
         device = torch.device("cuda", index)
         torch.cuda.set_device(index)
 
-    from . import hip_decoder, synth
+    from . import hip_decoder, pointnet2_utils, synth
     if args.decoder_dtype is not None:
         hip_decoder.set_mode(args.decoder_dtype)
     from .config import load_config
@@ -439,6 +441,7 @@ def main(argv=None):
         step(model, dd, config)
     e1.record()
     torch.cuda.synchronize()
+    pointnet2_utils.check_fps_cluster()      # (a large surface cloud is sampled by a workgroup cluster: no wait may have given up)
     ms = e0.elapsed_time(e1) / max(1, args.steps)
 
     props = torch.cuda.get_device_properties(index)

@@ -12,7 +12,9 @@ wrong-dtype or CPU tensors raise ``RuntimeError`` (NsdpHipError is a RuntimeErro
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
+import os
 
 import torch
 import torch.nn as nn
@@ -27,10 +29,108 @@ _c_int = ctypes.c_int
 # ------------------------------------------------------------------------------------------------
 # thin functional layer over the C ABI (one function per entry point of include/nsdp_hip.h)
 # ------------------------------------------------------------------------------------------------
+def _switch(value, default: bool) -> bool:
+    """An on/off knob from its environment text: unset or empty -> the default, "0" / "off" / "false" / "no" -> off, else on."""
+    if value is None or not value.strip():
+        return default
+    return value.strip().lower() not in ("0", "off", "false", "no")
+
+
+# Clouds of more than FPS_CLUSTER_MIN_POINTS - 1 points (and at most 262 144) are sampled by a cluster of workgroups
+# (include/nsdp_sampling.h, csrc/fps_cluster.hip) instead of the one-workgroup large-cloud kernel of nsdp_furthest_point_sampling;
+# the indices are the same.  NSDP_FPS_CLUSTER=0 / ``with fps_cluster(False):`` keeps the old kernel (the A/B partner).  Read when
+# a call runs, so a captured graph keeps the kernel it was captured with.
+FPS_CLUSTER = _switch(os.environ.get("NSDP_FPS_CLUSTER"), True)
+FPS_CLUSTER_MIN_POINTS = 8193       # the lower end of the default range (profiles/fps_cluster.txt)
+# The workspace of the latest cluster call on each (device, stream): what fps_cluster_status() reads when it is given none.  One
+# entry per stream, replaced by that stream's next call and dropped by the check, so nothing accumulates.
+_cluster_workspaces: dict = {}
+
+
+@contextlib.contextmanager
+def fps_cluster(on: bool):
+    """``with pointnet2_utils.fps_cluster(False): ...`` -- the large-cloud sampling kernel inside the block, restored after it."""
+    global FPS_CLUSTER
+    prev, FPS_CLUSTER = FPS_CLUSTER, bool(on)
+    try:
+        yield
+    finally:
+        FPS_CLUSTER = prev
+
+
+def fps_cluster_groups(n_max: int) -> int:
+    """Workgroups per cloud the cluster entries take by default: 0 where they do not serve (n_max <= 8192 or > 262 144)."""
+    return int(lib().nsdp_fps_cluster_groups(_c_int(int(n_max))))
+
+
+def _use_cluster(n_max: int) -> bool:
+    return FPS_CLUSTER and n_max >= FPS_CLUSTER_MIN_POINTS and fps_cluster_groups(n_max) != 0
+
+
+def _cluster_workspace(B, n_max, npoint, groups, device, workspace):
+    fn = lib().nsdp_fps_cluster_workspace_bytes
+    fn.restype = ctypes.c_size_t
+    need = int(fn(_c_int(B), _c_int(n_max), _c_int(int(npoint)), _c_int(int(groups))))
+    if need == 0 and B > 0 and int(npoint) > 0:
+        raise _lib.NsdpHipError(f"fps_cluster: no cluster of groups={int(groups)} for {n_max} points (1..32 workgroups of 8192 points; "
+                                "default only above 8192 points)")
+    if workspace is None:
+        workspace = torch.empty((need,), dtype=torch.uint8, device=device)
+    elif not (workspace.is_cuda and workspace.is_contiguous() and workspace.numel() * workspace.element_size() >= need):
+        raise _lib.NsdpHipError(f"fps_cluster: the workspace must be a contiguous GPU tensor of at least {need} bytes")
+    stream = stream_ptr()
+    _cluster_workspaces[(workspace.device.index, stream.value)] = (workspace, stream)
+    return workspace
+
+
+def furthest_point_sample_cluster(xyz: torch.Tensor, npoint: int, groups: int = 0, workspace=None) -> torch.Tensor:
+    """``furthest_point_sample`` by ``groups`` workgroups per cloud (include/nsdp_sampling.h; 0: ceil(N / 8192), for N above
+    8192): xyz (B,N,3) -> (B,npoint) int32, the same indices.  ``workspace``: a buffer of the caller's, else allocated here."""
+    with on_device(xyz):
+        B, N, C = xyz.shape
+        if C != 3:
+            raise _lib.NsdpHipError("xyz must be (B, N, 3)")
+        out = torch.empty((B, int(npoint)), dtype=torch.int32, device=xyz.device)
+        ws = _cluster_workspace(B, N, npoint, groups, xyz.device, workspace)
+        check(lib().nsdp_furthest_point_sampling_cluster(fptr(xyz, "xyz"), _c_int(B), _c_int(N), _c_int(int(npoint)),
+                                                         _c_int(int(groups)), optptr(ws), iptr(out), stream_ptr()),
+              "nsdp_furthest_point_sampling_cluster")
+    return out
+
+
+def fps_cluster_status(workspace=None) -> int:
+    """0, or the negative status (NSDP_ETIMEOUT) if a wait between the workgroups of a cloud gave up: the indices of that call
+    are in range and wrong.  With a ``workspace``: the call that last used it, after synchronising the current stream.  Without:
+    the latest cluster call of EVERY stream that made one since the last check (the side stream of the geometry pyramid and
+    the streams of a captured step included), each after synchronising its own stream; the record is dropped.  Not inside a
+    capture.  The kernels cannot hang or fault on a wait that runs out, so nothing reads this word unasked: a caller that runs
+    cluster calls of several streams at the same time checks it where it synchronises anyway (nsdp_amd.infer does)."""
+    if workspace is not None:
+        with on_device(workspace):
+            return int(lib().nsdp_fps_cluster_status(optptr(workspace), stream_ptr()))
+    worst = 0
+    while _cluster_workspaces:
+        _, (ws, stream) = _cluster_workspaces.popitem()
+        with on_device(ws):
+            worst = worst or int(lib().nsdp_fps_cluster_status(optptr(ws), stream))
+    return worst
+
+
+def check_fps_cluster() -> None:
+    """``fps_cluster_status()`` as an error: raises if a cluster call since the last check gave up a wait."""
+    rc = fps_cluster_status()
+    if rc:
+        raise _lib.NsdpHipError("farthest-point sampling by a workgroup cluster gave up a wait between workgroups (status "
+                                f"{rc}): its indices are wrong.  Cluster calls of several streams held the device at the same time; "
+                                "NSDP_FPS_CLUSTER=0 takes the one-workgroup kernel")
+
+
 def _fps(xyz: torch.Tensor, npoint: int) -> torch.Tensor:
     B, N, C = xyz.shape
     if C != 3:
         raise _lib.NsdpHipError("xyz must be (B, N, 3)")
+    if N > 8192 and xyz.is_cuda and _use_cluster(N):
+        return furthest_point_sample_cluster(xyz, npoint)
     out = torch.empty((B, int(npoint)), dtype=torch.int32, device=xyz.device)
     tmp = torch.empty((B, N), dtype=torch.float32, device=xyz.device) if N > 8192 else None
     with on_device(xyz):
@@ -88,17 +188,27 @@ def _packed_source(what, xyz, offsets, n_max):
     return cap, int(offsets.numel()) - 1, min(int(n_max), cap)
 
 
-def furthest_point_sample_ragged(xyz: torch.Tensor, offsets: torch.Tensor, npoint: int, n_max: int, idx_out=None):
+def furthest_point_sample_ragged(xyz: torch.Tensor, offsets: torch.Tensor, npoint: int, n_max: int, idx_out=None, groups: int = 0,
+                                 workspace=None):
     """``furthest_point_sample`` over a packed batch of clouds of different sizes (nsdp_amd.ragged): xyz (cap,3), offsets (B+1)
     int32 on the device, ``n_max`` = an upper bound of any shape's row count (it sizes the workgroup; the kernel clamps to it)
     -> idx (B,npoint) int32 of PACKED rows (offsets[b] + the index within shape b).  Minus its offset, a shape's row is the
     result of ``furthest_point_sample`` on that shape alone, ties included, whatever ``n_max`` is.  The host never reads
-    ``offsets``; ``idx_out``: a buffer of the caller's."""
+    ``offsets``; ``idx_out``: a buffer of the caller's.  With ``n_max`` above 8192 (and the FPS_CLUSTER knob on), or with an
+    explicit ``groups`` (1..32, ``n_max <= groups * 8192``), every shape is sampled by a cluster of workgroups
+    (include/nsdp_sampling.h; ``workspace``: a buffer of the caller's for it): the same indices."""
     with on_device(xyz):
         cap, B, n_max = _packed_source("furthest_point_sample_ragged", xyz, offsets, n_max)
         out = torch.empty((B, int(npoint)), dtype=torch.int32, device=xyz.device) if idx_out is None else idx_out
         if tuple(out.shape) != (B, int(npoint)):
             raise _lib.NsdpHipError(f"furthest_point_sample_ragged: idx_out must be ({B},{int(npoint)})")
+        if groups or (n_max > 8192 and _use_cluster(n_max)):
+            ws = _cluster_workspace(B, n_max, npoint, groups, xyz.device, workspace)
+            check(lib().nsdp_furthest_point_sampling_cluster_ragged(fptr(xyz, "xyz"), iptr(offsets, "offsets"), _c_int(B), _c_int(cap),
+                                                                    _c_int(n_max), _c_int(int(npoint)), _c_int(int(groups)),
+                                                                    optptr(ws), iptr(out, "idx_out"), stream_ptr()),
+                  "nsdp_furthest_point_sampling_cluster_ragged")
+            return out
         tmp = torch.empty((cap,), dtype=torch.float32, device=xyz.device) if n_max > 8192 else None
         check(lib().nsdp_furthest_point_sampling_ragged(fptr(xyz, "xyz"), iptr(offsets, "offsets"), _c_int(B), _c_int(cap),
                                                         _c_int(n_max), _c_int(int(npoint)), optptr(tmp), iptr(out, "idx_out"),
