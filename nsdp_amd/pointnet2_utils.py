@@ -125,6 +125,109 @@ def check_fps_cluster() -> None:
                                 "NSDP_FPS_CLUSTER=0 takes the one-workgroup kernel")
 
 
+# Exact k-nearest-neighbour search through a uniform cell grid (include/nsdp_search.h, csrc/knn_grid.hip): the indices and the
+# distance bits of the exhaustive scan (nsdp_knn / nsdp_knn_ragged_source) without its n x m distance tests.  NSDP_KNN_GRID:
+# "1" (default) = the grid where the source bound (m, n_max) is at least KNN_GRID_MIN_POINTS and queries x source rows per
+# shape at least KNN_GRID_MIN_TESTS, "0" = the scan everywhere (the A/B partner), "force" = the grid wherever its entries accept
+# the arguments.  Read when a call runs, so a captured graph keeps the kernels it was captured with.
+KNN_GRID_MODES = ("0", "1", "force")
+
+
+def _grid_mode(value, default: str = "1") -> str:
+    """NSDP_KNN_GRID's text -> "0" / "1" / "force": "force" by name, everything else as the on/off switch ``_switch`` parses."""
+    if value is not None and str(value).strip().lower() == "force":
+        return "force"
+    return "1" if _switch(None if value is None else str(value), default != "0") else "0"
+
+
+KNN_GRID = _grid_mode(os.environ.get("NSDP_KNN_GRID"))
+KNN_GRID_MIN_POINTS = 25000         # the smallest measured source bound from which the grid wins (profiles/knn_grid.txt)
+KNN_GRID_MIN_TESTS = 12_500_000     # ... and the smallest queries x source rows per shape: 500 centres x 25 000 points
+KNN_GRID_MAX_K, KNN_GRID_MAX_POINTS = 32, 1 << 20      # the limits of the entries
+# The workspace of the latest grid search on each (device, stream): what knn_grid_stats() reads when it is given none.  One entry
+# per stream, replaced by that stream's next search and dropped by the read, so nothing accumulates -- but the entry keeps that
+# one workspace allocated (up to 25 MB per shape at 128 cells per axis) until then: forget_knn_grid_stats() drops all of them.
+_grid_workspaces: dict = {}
+
+
+@contextlib.contextmanager
+def knn_grid_mode(mode):
+    """``with pointnet2_utils.knn_grid_mode("0"): ...`` -- "0" / "1" / "force" (or False / True) inside the block, the previous
+    mode restored after it."""
+    global KNN_GRID
+    mode = {True: "1", False: "0"}.get(mode, mode)
+    if mode not in KNN_GRID_MODES:
+        raise ValueError(f"knn_grid_mode: one of {KNN_GRID_MODES}, got {mode!r}")
+    prev, KNN_GRID = KNN_GRID, mode
+    try:
+        yield
+    finally:
+        KNN_GRID = prev
+
+
+def _grid_accepts(B: int, m: int, k: int) -> bool:
+    return 1 <= int(k) <= min(KNN_GRID_MAX_K, m) and m <= KNN_GRID_MAX_POINTS and 1 <= B <= 65535
+
+
+def _use_grid(t: torch.Tensor, B: int, n: int, m: int, k: int) -> bool:
+    """The dispatch of ``knn`` / ``knn_ragged_source``: n queries against (at most) m source rows per shape."""
+    if KNN_GRID == "0" or not t.is_cuda or n <= 0 or not _grid_accepts(B, m, k):
+        return False
+    return KNN_GRID == "force" or (m >= KNN_GRID_MIN_POINTS and n * m >= KNN_GRID_MIN_TESTS)
+
+
+def _grid_workspace(B, queries, source_rows, m_max, device, workspace):
+    fn = lib().nsdp_knn_grid_workspace_bytes
+    fn.restype = ctypes.c_size_t
+    need = int(fn(_c_int(B), _c_int(queries), _c_int(source_rows), _c_int(m_max)))
+    if workspace is None:
+        workspace = torch.empty((need,), dtype=torch.uint8, device=device)
+    elif not (workspace.is_cuda and workspace.is_contiguous() and workspace.numel() * workspace.element_size() >= need):
+        raise _lib.NsdpHipError(f"knn_grid: the workspace must be a contiguous GPU tensor of at least {need} bytes")
+    # (not during a capture: a workspace from the graph's private pool would stay pinned for counters that cannot be read there)
+    if need and not torch.cuda.is_current_stream_capturing():
+        stream = stream_ptr()
+        _grid_workspaces[(workspace.device.index, stream.value)] = workspace
+    return workspace
+
+
+def knn_grid(query: torch.Tensor, source: torch.Tensor, k: int, return_dist: bool = False, workspace=None):
+    """``knn`` through the cell grid (include/nsdp_search.h), at any size its entries accept: query (B,n,3), source (B,m,3) ->
+    idx (B,n,k) int32 (and dist2), the bits of ``knn``.  ``workspace``: a buffer of the caller's, else allocated here."""
+    with on_device(query):
+        if query.dim() != 3 or query.shape[2] != 3 or source.dim() != 3 or source.shape[2] != 3 or source.shape[0] != query.shape[0]:
+            raise _lib.NsdpHipError(f"knn_grid: query (B,n,3) and source (B,m,3), got {tuple(query.shape)}, {tuple(source.shape)}")
+        B, n, m = int(query.shape[0]), int(query.shape[1]), int(source.shape[1])
+        idx = torch.empty((B, n, int(k)), dtype=torch.int32, device=query.device)
+        d2 = torch.empty((B, n, int(k)), dtype=torch.float32, device=query.device) if return_dist else None
+        ws = _grid_workspace(B, B * n, B * m, m, query.device, workspace)
+        check(lib().nsdp_knn_grid(fptr(query, "query"), fptr(source, "source"), _c_int(B), _c_int(n), _c_int(m), _c_int(int(k)),
+                                  optptr(ws), iptr(idx), optptr(d2), stream_ptr()), "nsdp_knn_grid")
+    return (idx, d2) if return_dist else idx
+
+
+def forget_knn_grid_stats() -> None:
+    """Drops the remembered workspaces of ``knn_grid_stats()`` (their memory goes back to the allocator)."""
+    _grid_workspaces.clear()
+
+
+def knn_grid_stats(workspace=None):
+    """What the grid search that last used ``workspace`` did, after synchronising the current stream: a dict of ``queries``,
+    ``tests`` (distance tests), ``scanned`` (queries finished by the plain scan) and ``cells`` (cells allocated).  Without a
+    workspace: the latest search on the current stream, whose record is dropped -- None if there has been none since the last
+    read.  Not inside a capture."""
+    if workspace is None:
+        if not torch.cuda.is_available():
+            return None
+        workspace = _grid_workspaces.pop((torch.cuda.current_device(), stream_ptr().value), None)
+        if workspace is None:
+            return None
+    with on_device(workspace):
+        out = (ctypes.c_int64 * 4)()
+        check(lib().nsdp_knn_grid_stats(optptr(workspace), stream_ptr(), out), "nsdp_knn_grid_stats")
+    return {"queries": int(out[0]), "tests": int(out[1]), "scanned": int(out[2]), "cells": int(out[3])}
+
+
 def _fps(xyz: torch.Tensor, npoint: int) -> torch.Tensor:
     B, N, C = xyz.shape
     if C != 3:
@@ -145,6 +248,8 @@ def knn(query: torch.Tensor, source: torch.Tensor, k: int, return_dist: bool = F
     query (B,n,3), source (B,m,3) -> idx (B,n,k) int32 ascending by (distance, index)."""
     B, n, _ = query.shape
     m = source.shape[1]
+    if _use_grid(query, int(B), int(n), int(m), k):      # large clouds: the cell grid, the same bits
+        return knn_grid(query, source, k, return_dist)
     idx = torch.empty((B, n, int(k)), dtype=torch.int32, device=query.device)
     d2 = torch.empty((B, n, int(k)), dtype=torch.float32, device=query.device) if return_dist else None
     with on_device(query):
@@ -216,23 +321,18 @@ def furthest_point_sample_ragged(xyz: torch.Tensor, offsets: torch.Tensor, npoin
     return out
 
 
-def knn_ragged_source(query: torch.Tensor, source: torch.Tensor, offsets: torch.Tensor, k: int, n_max: int, query_offsets=None,
-                      return_dist: bool = False, idx_out=None, dist_out=None):
-    """``knn`` against a packed source set: source (cap,3), offsets (B+1) int32 on the device, ``n_max`` as above.  The queries
-    are rectangular (B,n,3) -> idx (B,n,k), or packed themselves, (qcap,3) with ``query_offsets`` (B+1) -> idx (qcap,k); the
-    self-search of a packed cloud is ``knn_ragged_source(xyz, xyz, offsets, k, n_max, query_offsets=offsets)``.  The indices
-    are PACKED rows of ``source``; minus the shape's offset they, and the distance bits, are those of ``knn`` on that shape
-    alone.  Rows of a packed query set at or beyond query_offsets[B] are not written (``idx_out`` / ``dist_out``: buffers of
-    the caller's).  The host never reads either offsets tensor."""
+def _knn_ragged_source(grid, query, source, offsets, k, n_max, query_offsets, return_dist, idx_out, dist_out, workspace=None):
+    """The body of ``knn_ragged_source`` / ``knn_grid_ragged_source``.  grid: None = by the dispatch, True = the grid entry."""
+    what = "knn_grid_ragged_source" if grid else "knn_ragged_source"
     with on_device(query):
-        cap, B, n_max = _packed_source("knn_ragged_source", source, offsets, n_max)
+        cap, B, n_max = _packed_source(what, source, offsets, n_max)
         if query_offsets is None:
             if query.dim() != 3 or query.shape[2] != 3 or query.shape[0] != B:
-                raise _lib.NsdpHipError(f"knn_ragged_source: rectangular queries must be ({B},n,3), got {tuple(query.shape)}")
+                raise _lib.NsdpHipError(f"{what}: rectangular queries must be ({B},n,3), got {tuple(query.shape)}")
             n, qcap, lead = int(query.shape[1]), 0, (B, int(query.shape[1]))
         else:
             if query.dim() != 2 or query.shape[1] != 3 or query_offsets.numel() != B + 1:
-                raise _lib.NsdpHipError(f"knn_ragged_source: packed queries must be (qcap,3) with {B + 1} offsets, got "
+                raise _lib.NsdpHipError(f"{what}: packed queries must be (qcap,3) with {B + 1} offsets, got "
                                         f"{tuple(query.shape)}, {query_offsets.numel()}")
             n, qcap, lead = 0, int(query.shape[0]), (int(query.shape[0]),)
         want = lead + (int(k),)
@@ -240,14 +340,41 @@ def knn_ragged_source(query: torch.Tensor, source: torch.Tensor, offsets: torch.
         d2 = dist_out if dist_out is not None else (
             torch.empty(want, dtype=torch.float32, device=query.device) if return_dist else None)
         if tuple(idx.shape) != want or (d2 is not None and tuple(d2.shape) != want):
-            raise _lib.NsdpHipError(f"knn_ragged_source: output buffers must be {want}")
-        check(lib().nsdp_knn_ragged_source(fptr(query, "query"), optptr(None) if query_offsets is None else iptr(query_offsets, "query_offsets"),
-                                           fptr(source, "source"), iptr(offsets, "offsets"), _c_int(B), _c_int(n), _c_int(qcap),
-                                           _c_int(cap), _c_int(n_max), _c_int(int(k)), iptr(idx, "idx_out"),
-                                           optptr(None) if d2 is None else fptr(d2, "dist_out"), stream_ptr()),
-              "nsdp_knn_ragged_source")
+            raise _lib.NsdpHipError(f"{what}: output buffers must be {want}")
+        qptr = optptr(None) if query_offsets is None else iptr(query_offsets, "query_offsets")
+        dptr = optptr(None) if d2 is None else fptr(d2, "dist_out")
+        # (a shape of a packed query set has at most n_max rows when it is the source itself, and at most qcap otherwise)
+        per_shape = n if query_offsets is None else min(qcap, n_max if query_offsets is offsets else qcap)
+        if grid or (grid is None and _use_grid(query, B, per_shape, n_max, k)):
+            ws = _grid_workspace(B, qcap if query_offsets is not None else B * n, cap, n_max, query.device, workspace)
+            check(lib().nsdp_knn_grid_ragged_source(fptr(query, "query"), qptr, fptr(source, "source"), iptr(offsets, "offsets"),
+                                                    _c_int(B), _c_int(n), _c_int(qcap), _c_int(cap), _c_int(n_max), _c_int(int(k)),
+                                                    optptr(ws), iptr(idx, "idx_out"), dptr, stream_ptr()),
+                  "nsdp_knn_grid_ragged_source")
+        else:
+            check(lib().nsdp_knn_ragged_source(fptr(query, "query"), qptr, fptr(source, "source"), iptr(offsets, "offsets"), _c_int(B),
+                                               _c_int(n), _c_int(qcap), _c_int(cap), _c_int(n_max), _c_int(int(k)),
+                                               iptr(idx, "idx_out"), dptr, stream_ptr()), "nsdp_knn_ragged_source")
     return (idx, d2) if (return_dist or dist_out is not None) else idx
 
+
+def knn_ragged_source(query: torch.Tensor, source: torch.Tensor, offsets: torch.Tensor, k: int, n_max: int, query_offsets=None,
+                      return_dist: bool = False, idx_out=None, dist_out=None):
+    """``knn`` against a packed source set: source (cap,3), offsets (B+1) int32 on the device, ``n_max`` as above.  The queries
+    are rectangular (B,n,3) -> idx (B,n,k), or packed themselves, (qcap,3) with ``query_offsets`` (B+1) -> idx (qcap,k); the
+    self-search of a packed cloud is ``knn_ragged_source(xyz, xyz, offsets, k, n_max, query_offsets=offsets)``.  The indices
+    are PACKED rows of ``source``; minus the shape's offset they, and the distance bits, are those of ``knn`` on that shape
+    alone.  Rows of a packed query set at or beyond query_offsets[B] are not written (``idx_out`` / ``dist_out``: buffers of
+    the caller's).  The host never reads either offsets tensor.  Large clouds go through the cell grid (KNN_GRID above): the
+    same bits."""
+    return _knn_ragged_source(None, query, source, offsets, k, n_max, query_offsets, return_dist, idx_out, dist_out)
+
+
+def knn_grid_ragged_source(query: torch.Tensor, source: torch.Tensor, offsets: torch.Tensor, k: int, n_max: int, query_offsets=None,
+                           return_dist: bool = False, idx_out=None, dist_out=None, workspace=None):
+    """``knn_ragged_source`` through the cell grid (include/nsdp_search.h), at any size its entries accept: the same arguments
+    and the same bits.  ``workspace``: a buffer of the caller's, else allocated here."""
+    return _knn_ragged_source(True, query, source, offsets, k, n_max, query_offsets, return_dist, idx_out, dist_out, workspace)
 
 def nn_dist2(query: torch.Tensor, source: torch.Tensor, return_index: bool = False):
     """The squared distance of every query point to its nearest source point (include/nsdp_eval.h): query (B,n,3), source
