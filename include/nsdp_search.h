@@ -7,8 +7,10 @@
  * conservative lower bound of the distance to any point not yet visited.  The list is ordered by the pair (distance, index), a
  * strict total order, and the distance is the scan's expression (nsdp::sq_dist3, one rounding per operation): the k best are
  * unique, so the indices and the distance bits are those of the scan entries, exact ties and duplicates included, whatever
- * order the binning leaves the points in.  A query whose shells would exceed a fixed radius (a far outlier) is finished by a
- * plain scan of its shape.
+ * order the binning leaves the points in.  The bound is formed in the box's own frame (coordinates minus the box's corner), so
+ * it does not depend on where the cloud sits.  A query opens shells while its rows read plus distance tests stay within 64 + m / 4
+ * (none if it lies farther outside the box than the box's largest extent); one that gives up (a far outlier, a query far
+ * outside) is finished by an exhaustive scan of its shape that the 64 lanes of its wave carry out together.
  *
  * The conventions are those of nsdp_sampling.h: device pointers + sizes, outputs and the workspace allocated by the caller and
  * possibly UNINITIALISED on entry, `stream` a hipStream_t passed as void*, 0 / negative NSDP_E* / positive hipError_t as the
@@ -22,7 +24,8 @@
  * to m = k = 1.  Non-finite coordinates are out of contract for the result, as in nsdp_knn; they cannot form an address
  * outside the workspace (a cell coordinate is clamped as a float, NaN to cell 0, before it becomes an integer).
  *
- * tests/test_knn_grid_arena_gpu.py holds the two launching entries to this inside the poisoned arena.
+ * tests/test_knn_grid_arena_gpu.py holds the two launching entries to this inside the poisoned arena, and
+ * tests/test_knn_grid_anywhere_arena_gpu.py on clouds far from the origin, volumes and queries that all take the finish.
  */
 #ifndef NSDP_SEARCH_H_
 #define NSDP_SEARCH_H_
@@ -55,7 +58,7 @@ int nsdp_knn_grid_ragged_source(const float *query, const int32_t *query_offsets
                                 float *dist_out, void *stream);
 
 /* Synchronises `stream` and reports on the call that last used the workspace: out = {queries, distance tests, queries
- * finished by the plain scan, cells allocated}.  (Each workgroup of the search leaves one partial in the workspace; this call
+ * finished by the exhaustive scan, cells allocated}.  (Each workgroup of the search leaves one partial in the workspace; this call
  * sums them on the host.) */
 int nsdp_knn_grid_stats(const void *workspace, void *stream, int64_t out[4]);
 

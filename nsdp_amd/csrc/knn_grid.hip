@@ -8,9 +8,10 @@
 //   memset     the zeroed part of the workspace: the search's partial counters, the per-shape cursors, the raw bounds, the cell
 //              counts;
 //   bounds     per shape the bounding box of its own rows, fp32, by integer atomic maxima over order-preserving encodings;
-//   params     per shape: cell side h = largest extent / Gs, 1/h, the cell counts per axis g = cell(hi) + 1 <= Gs, the slack of
-//              the stop rule; G = min(128, ceil(sqrt(m_max / 4))) is a host number (m_max = m or n_max), so the cell arrays have
-//              a host-known size, G^3 cells per shape, and Gs = min(G, ceil(sqrt(m_s / 4))) follows the shape's own row count;
+//   params     per shape: cell side h = largest extent / Gs, 1/h, the cell counts per axis g = cell(hi) + 1 <= Gs, the extent
+//              and the slack of the stop rule; G = min(128, ceil(sqrt(m_max / 4))) is a host number (m_max = m or n_max), so
+//              the cell arrays have a host-known size, G^3 cells per shape, and Gs = min(G, ceil(sqrt(m_s / 4))) follows the
+//              shape's own row count;
 //   count      one lane per source point: its cell, one integer atomic;
 //   ranges     every cell gets a range [start, end) of the shape's m slots: a block scan of 1024 counts and one atomic per
 //              workgroup on the shape's cursor -- the blocks lie in whatever order the workgroups arrive, the ranges inside
@@ -28,24 +29,61 @@
 // Exactness.  The list is ordered by the pair (distance, index) -- insert when d < bd[u] || (d == bd[u] && j < bi[u]) -- a
 // strict total order, and d is nsdp::sq_dist3 with contraction off, the scan's bits.  The k smallest pairs of a set are unique,
 // so the result does not depend on the order in which candidates arrive: it equals the scan's as soon as every point that can
-// enter the list has been seen.  After shell R the visited block is [c - R, c + R] per axis (cut to the grid).  A point outside
-// it has, on some axis, a cell above c + R or below c - R.  The cell function is monotone in the coordinate, so such a point lies
-// beyond that face of the block: its coordinate is at least lo + (c + R + 1) * h - slack (at most lo + (c - R) * h + slack), where
-// slack = 2^-18 * max|coordinate of the box| covers the roundings of (p - lo) * (1/h), of 1/h against h, and of the edge
-// expression (together below 2^-20 of that maximum).  The smallest such gap over the faces that still have cells beyond them,
-// minus slack, squared and scaled by (1 - 2^-19), is below the computed distance of any unvisited point (the five roundings of
-// sq_dist3 and the three of the bound lose less than 2^-20 relatively; d >= dx * dx on the offending axis).  The query stops
-// when its k-th distance is STRICTLY below that bound -- an unvisited point can then not even tie -- or when the block covers
-// the whole grid.  A query still open after shell kMaxRadius (a far outlier, a query far outside the box) empties its list and
-// scans its shape's rows: exact by construction.
+// enter the list has been seen.
 //
-// Limits.  (1) slack is absolute in the coordinates' magnitude while the cell side follows the extent: a cloud far from the
-// origin relative to its size (extent 1 around 2000: slack 7.6e-3 against cells of about 1e-2) loses its pruning, every shell's
-// bound is 0 and the queries take the plain-scan finish, one lane each: exact, and far slower than the scan.  Centre such
-// data, or NSDP_KNN_GRID=0.  (2) G follows sqrt(m / 4), the density of a SURFACE (about G^2 of the G^3 cells occupied, four
-// points each).  A cloud that fills its box's volume has 8 / sqrt(m) points per cell at that G (0.025 at 100 000 points), the
-// 729 cells of kMaxRadius then hold about k points, and many queries take the plain-scan finish as well.  The encoder's
-// clouds are centred surfaces; nsdp_knn_grid_stats shows the plain scans of anything else.
+// The stop rule lives in the box's own frame u = fl(p - lo), the first operation of the cell function, so nothing in it scales
+// with where the cloud sits.  Roundings are written (1 + e), |e| <= 2^-24; ext is the largest extent, h = fl(ext / Gs).
+//   cell    c(p) = clamp(floor(fl(u_p * inv_h))), inv_h = fl(1 / h) = (1 + e2) / h.  After shell R the visited block is
+//           [c - R, c + R] per axis (cut to the grid).  An unvisited point has, on some axis, a cell >= e = c + R + 1 or
+//           <= c - R - 1.  Rounding is monotone and e is a float, so fl(u_p * inv_h) >= e gives u_p * inv_h >= e (1 - 2^-24),
+//           and fl(u_p * inv_h) < e (e = c - R) gives u_p * inv_h < e.  The clamp keeps both (a clamped cell lies between 0 and
+//           floor of the product).  With the edge E = fl(e * h) = e h (1 + e3):  u_p >= E (1 - 2^-22), resp. u_p < E (1 + 2^-22).
+//           Every e used is <= g - 1 <= Gs - 1, so 0 <= E <= ext.
+//   frame   u_p = (p - lo)(1 + ep), uq = fl(q - lo) = (q - lo)(1 + eq): relative to |u|, not to |p|.  The true difference is
+//           p - q = u_p / (1 + ep) - uq / (1 + eq), increasing in u_p >= 0, hence
+//           p - q >= E - uq - 2^-21 ext - 2^-23 |uq|   (and q - p >= uq - E - the same) for every unvisited point.
+//   gap     the kernel forms fl(fl(E - uq) - s) with s = 2^-20 ext + 2^-22 |uq|: the inner subtraction errs by at most
+//           2^-24 (E + |uq|), so s covers the frame's terms and this one with a factor 1.8 to spare (which also swallows the
+//           rounding of s itself); the outer subtraction errs by 2^-24 of the gap.  So gap <= |p - q| (1 + 2^-24) on the offending
+//           axis, taken as the smallest over the faces that still have cells beyond them.
+//   bound   fl(fl(gap * gap) * (1 - 2^-19)) <= |p - q|^2 (1 - 2^-19.3), for gaps in [1e-15, 1e18] whose squares are normal
+//           numbers; any other gap proves nothing (bound 0).  The computed distance is at least fl(dx * dx) with dx = fl(q - p)
+//           (adding non-negative terms and rounding cannot go below a float already reached), >= |p - q|^2 (1 - 2^-24)^3.
+// So bound is STRICTLY below the computed sq_dist3 of every unvisited point, wherever the cloud sits: the slack follows the
+// extent, plus a term in |uq| that matters only for queries outside the box.  A box whose extent is a few ulps of its offset
+// changes nothing: u is then exact, and the argument never used the size of lo.  The query stops when its k-th distance is
+// strictly below the bound -- an unvisited point can then not even tie -- or when the block covers the whole grid.
+//
+// Budget.  Shells are opened while that is cheaper than the exhaustive finish.  A query counts its work, one per row of cells
+// read and one per distance test, and gives up when the count passes kBudgetFloor + m / kBudgetShare: a wave whose lanes all
+// need the finish pays m steps for it, a wave with one such lane m / 64, and the shells of a query run in one divergent lane;
+// m / 4 lies between the two and is 1.7 times the most a clustered surface was seen to need.  A query farther
+// outside the box than the box's largest extent, on any axis, gets no budget: its neighbours are spread over the side of the
+// cloud that faces it, the faces on the other axes stay closer than its k-th distance until the block has all but covered
+// them, and the rule ends, if at all, after most of the grid's rows and most of the m tests.  (An argument, NOT measured: no
+// build gave such queries a budget.  What they cost without one is measured: 500 queries 1.2 to 2.5 extents outside take
+// the finish in 18.1 ms, as the 50-sigma ones do.)
+//
+// Finish.  The lanes that gave up empty their lists, and the WAVE scans the shape's rows for them, 64 consecutive rows per load,
+// coalesced, in one of two forms chosen per wave by the number of its needy lanes:
+//   queries broadcast (up to kCrowd needy lanes, K <= 16)   for each needy lane in turn its query and its k-th pair are
+//           broadcast, every lane tests its own row, a ballot marks the candidates that beat the k-th pair under the same
+//           (distance, index) order, and the owner lane inserts them with the same `consider` into the same registers: m / 64
+//           steps per needy lane.
+//   rows broadcast (more needy lanes; always at K = 32)      each row in turn is broadcast, every needy lane tests it against
+//           its own query and inserts into its own list, all of them side by side: m steps, whatever the number of needy lanes.
+// Exact by construction; the order of arrival is irrelevant as above.  Every lane of the wave takes part, also lanes without a
+// query, and all loop bounds are wave-uniform.  No LDS, no barrier.  Measured, 500 far queries against 100 000 points, k = 16
+// (profiles/knn_grid_anywhere.txt): rows broadcast 18.2 ms, queries broadcast 25.4 ms, one plain scan per lane (the parent) 20.1 ms.
+// The first costs a wave the same whatever its needy lanes, the second grows with their number, so they meet at 64 * 18.2 /
+// 25.4 = 45.7 needy lanes: kCrowd = 45.  K = 32 has the second form alone: see the kernel.
+//
+// Limits.  G follows sqrt(m / 4), the density of a SURFACE, and is one number per shape.  A volume-filling cloud has 8 / sqrt(m)
+// points per cell and walks several hundred mostly empty rows per query; a cluster that falls into a handful of cells costs
+// every query near it all the points of those cells.  Both are exact and pruned, neither is what the grid was sized for; a
+// density-adaptive grid is not built.  Queries other than the self-search are not binned.  A call whose queries ALL take the
+// finish (500 far queries against 100 000 points: 18.2 ms, the parent 20.1, the scan kernel 1.6) is the scan's work done by 8
+// waves: the scan wins it, and the dispatch cannot know.
 #include <cfloat>
 #include <climits>
 #include <vector>
@@ -61,7 +99,10 @@
 namespace {
 
 constexpr int kMaxGrid = 128;                 // cells per axis at most
-constexpr int kMaxRadius = 4;                 // shells before the plain-scan finish (9^3 = 729 cells visited by then)
+constexpr int kBudgetShare = 4;               // a query opens shells until its rows read + tests pass kBudgetFloor + m / kBudgetShare
+constexpr int kBudgetFloor = 64;
+constexpr int kBothFormsMaxK = 16;            // longer lists: the row-broadcast finish alone
+constexpr int kCrowd = 45;                    // more needy lanes in a wave than this: the finish broadcasts rows, not queries
 constexpr int kMaxK = 32;
 constexpr int kMaxPoints = 1 << 20;           // source points per shape
 constexpr int kSearchLanes = 64;              // queries per workgroup of the search
@@ -160,7 +201,7 @@ __device__ __forceinline__ bool source_tile(const int32_t *__restrict__ offsets,
 }
 
 struct Grid {
-  float lox, loy, loz, inv_h, h, slack;
+  float lox, loy, loz, inv_h, h, slack, ext;
   int gx, gy, gz;
 };
 
@@ -170,7 +211,7 @@ __device__ __forceinline__ Grid load_grid(const float *__restrict__ params, int 
   const int4 g = *reinterpret_cast<const int4 *>(params + static_cast<size_t>(b) * 16 + 8);
   Grid r;
   r.lox = a.x; r.loy = a.y; r.loz = a.z; r.inv_h = a.w;
-  r.h = c.x; r.slack = c.y;
+  r.h = c.x; r.slack = c.y; r.ext = c.z;
   // (read back from memory: clamped, so that nothing downstream depends on what the workspace holds)
   r.gx = min(max(g.x, 1), G); r.gy = min(max(g.y, 1), G); r.gz = min(max(g.z, 1), G);
   return r;
@@ -259,7 +300,7 @@ __global__ __launch_bounds__(256) void knn_grid_params_kernel(const unsigned *__
   int4 g = make_int4(1, 1, 1, 0);
   if (ok) {
     a = make_float4(lox, loy, loz, inv_h);
-    c = make_float4(h, big * 0x1p-18f, 0.f, 0.f);
+    c = make_float4(h, ext * 0x1p-20f, ext, 0.f);      // (the stop rule's slack follows the extent: see Exactness)
     g = make_int4(axis_cell(hix, lox, inv_h, Gs) + 1, axis_cell(hiy, loy, inv_h, Gs) + 1, axis_cell(hiz, loz, inv_h, Gs) + 1, 0);
   }
   float *p = params + static_cast<size_t>(b) * 16;
@@ -370,12 +411,39 @@ __global__ __launch_bounds__(kSearchLanes) void knn_grid_search_kernel(
     idx_base = 0;
     idx_max = INT_MAX;
   }
-  const int row = row0 + static_cast<int>(threadIdx.x);
+  const int row = row0 + static_cast<int>(threadIdx.x), lane = static_cast<int>(threadIdx.x);
+  const bool live = row < qend;      // (a lane without a query still takes part in the finish of the others)
   unsigned tests = 0, scanned = 0, queries = 0;
-  if (row < qend) {
+  float qx = 0.f, qy = 0.f, qz = 0.f;
+  size_t out_row = 0;
+  float bd[K];
+  int bi[K];
+#pragma unroll
+  for (int t = 0; t < K; ++t) {
+    bd[t] = FLT_MAX;      // an empty slot: (FLT_MAX, -1) lets no candidate at FLT_MAX in, as the scan's `d < FLT_MAX` does not
+    bi[t] = -1;
+  }
+  auto consider = [&](float d, int j) __attribute__((always_inline)) {
+    if (d < bd[K - 1] || (d == bd[K - 1] && j < bi[K - 1])) {
+#pragma unroll
+      for (int u = K - 1; u > 0; --u) {
+        const bool shift = d < bd[u - 1] || (d == bd[u - 1] && j < bi[u - 1]);
+        const bool here = !shift && (d < bd[u] || (d == bd[u] && j < bi[u]));
+        const float nd = shift ? bd[u - 1] : (here ? d : bd[u]);
+        const int ni = shift ? bi[u - 1] : (here ? j : bi[u]);
+        bd[u] = nd;
+        bi[u] = ni;
+      }
+      if (d < bd[0] || (d == bd[0] && j < bi[0])) {
+        bd[0] = d;
+        bi[0] = j;
+      }
+    }
+  };
+  bool done = true;
+  if (live) {
     queries = 1;
-    float qx, qy, qz;
-    size_t out_row = static_cast<size_t>(row);
+    out_row = static_cast<size_t>(row);
     if (self && row - qlo < m) {      // the self-search in cell order: this lane's query is a sorted point, its row that point's
       const float4 P = sorted[static_cast<size_t>(lo) + (row - qlo)];
       qx = P.x; qy = P.y; qz = P.z;
@@ -384,36 +452,19 @@ __global__ __launch_bounds__(kSearchLanes) void knn_grid_search_kernel(
       const float *qp = query + static_cast<size_t>(row) * 3;
       qx = qp[0]; qy = qp[1]; qz = qp[2];
     }
-    float bd[K];
-    int bi[K];
-#pragma unroll
-    for (int t = 0; t < K; ++t) {
-      bd[t] = FLT_MAX;      // an empty slot: (FLT_MAX, -1) lets no candidate at FLT_MAX in, as the scan's `d < FLT_MAX` does not
-      bi[t] = -1;
-    }
-    auto consider = [&](float d, int j) __attribute__((always_inline)) {
-      if (d < bd[K - 1] || (d == bd[K - 1] && j < bi[K - 1])) {
-#pragma unroll
-        for (int u = K - 1; u > 0; --u) {
-          const bool shift = d < bd[u - 1] || (d == bd[u - 1] && j < bi[u - 1]);
-          const bool here = !shift && (d < bd[u] || (d == bd[u] && j < bi[u]));
-          const float nd = shift ? bd[u - 1] : (here ? d : bd[u]);
-          const int ni = shift ? bi[u - 1] : (here ? j : bi[u]);
-          bd[u] = nd;
-          bi[u] = ni;
-        }
-        if (d < bd[0] || (d == bd[0] && j < bi[0])) {
-          bd[0] = d;
-          bi[0] = j;
-        }
-      }
-    };
     const Grid g = load_grid(params, b, G);
     const int cx = axis_cell(qx, g.lox, g.inv_h, g.gx), cy = axis_cell(qy, g.loy, g.inv_h, g.gy), cz = axis_cell(qz, g.loz, g.inv_h, g.gz);
+    // the query in the box's frame, the first operation of axis_cell: the stop rule's arithmetic stays there (see Exactness)
+    const float ux = __fsub_rn(qx, g.lox), uy = __fsub_rn(qy, g.loy), uz = __fsub_rn(qz, g.loz);
+    const float sx = g.slack + 0x1p-22f * fabsf(ux), sy = g.slack + 0x1p-22f * fabsf(uy), sz = g.slack + 0x1p-22f * fabsf(uz);
+    // rows read + tests this query may spend on shells; none for a query farther outside the box than the box is wide
+    const bool far = ux < -g.ext || ux > 2.f * g.ext || uy < -g.ext || uy > 2.f * g.ext || uz < -g.ext || uz > 2.f * g.ext;
+    const unsigned budget = far ? 0u : static_cast<unsigned>(kBudgetFloor + m / kBudgetShare);
+    unsigned reads = 0;
     const int2 *cells = ranges + static_cast<size_t>(b) * C;
     const float4 *pts = sorted + static_cast<size_t>(lo);
-    bool done = false;
-    for (int R = 0; R <= kMaxRadius && !done; ++R) {
+    done = false;
+    for (int R = 0; R < kMaxGrid; ++R) {      // (shell kMaxGrid - 1 covers any grid)
       const int z0 = max(cz - R, 0), z1 = min(cz + R, g.gz - 1), y0 = max(cy - R, 0), y1 = min(cy + R, g.gy - 1);
       for (int z = z0; z <= z1; ++z)
         for (int y = y0; y <= y1; ++y) {
@@ -433,6 +484,7 @@ __global__ __launch_bounds__(kSearchLanes) void knn_grid_search_kernel(
             const int xe = face ? min(xb, x + (kRangeBlock - 1 - (c & (kRangeBlock - 1)))) : x;
             const int first = cells[c].x, last = cells[row_base + xe].y;
             const int j0 = min(max(first, 0), m), j1 = min(max(last, j0), m);
+            ++reads;
             if (j0 < j1) {
               float4 P = pts[j0];
               for (int j = j0; j < j1; ++j) {
@@ -450,35 +502,114 @@ __global__ __launch_bounds__(kSearchLanes) void knn_grid_search_kernel(
                  more_z0 = cz - R > 0, more_z1 = cz + R < g.gz - 1;
       if (!(more_x0 || more_x1 || more_y0 || more_y1 || more_z0 || more_z1)) {
         done = true;      // the block covers the grid: every point of the shape has been seen
-      } else {
-        float kth = bd[0];
-#pragma unroll
-        for (int t = 1; t < K; ++t) kth = (t == k - 1) ? bd[t] : kth;
-        float gap = FLT_MAX;
-        if (more_x0) gap = fminf(gap, (qx - (g.lox + static_cast<float>(cx - R) * g.h)) - g.slack);
-        if (more_x1) gap = fminf(gap, ((g.lox + static_cast<float>(cx + R + 1) * g.h) - qx) - g.slack);
-        if (more_y0) gap = fminf(gap, (qy - (g.loy + static_cast<float>(cy - R) * g.h)) - g.slack);
-        if (more_y1) gap = fminf(gap, ((g.loy + static_cast<float>(cy + R + 1) * g.h) - qy) - g.slack);
-        if (more_z0) gap = fminf(gap, (qz - (g.loz + static_cast<float>(cz - R) * g.h)) - g.slack);
-        if (more_z1) gap = fminf(gap, ((g.loz + static_cast<float>(cz + R + 1) * g.h) - qz) - g.slack);
-        // (a gap too small to square without underflow, or so large that its square overflows, proves nothing)
-        const float bound = (gap > 1e-15f && gap < 1e18f) ? (gap * gap) * (1.0f - 0x1p-19f) : 0.f;
-        done = kth < FLT_MAX && kth < bound;
+        break;
       }
+      float kth = bd[0];
+#pragma unroll
+      for (int t = 1; t < K; ++t) kth = (t == k - 1) ? bd[t] : kth;
+      float gap = FLT_MAX;
+      if (more_x0) gap = fminf(gap, (ux - static_cast<float>(cx - R) * g.h) - sx);
+      if (more_x1) gap = fminf(gap, (static_cast<float>(cx + R + 1) * g.h - ux) - sx);
+      if (more_y0) gap = fminf(gap, (uy - static_cast<float>(cy - R) * g.h) - sy);
+      if (more_y1) gap = fminf(gap, (static_cast<float>(cy + R + 1) * g.h - uy) - sy);
+      if (more_z0) gap = fminf(gap, (uz - static_cast<float>(cz - R) * g.h) - sz);
+      if (more_z1) gap = fminf(gap, (static_cast<float>(cz + R + 1) * g.h - uz) - sz);
+      // (a gap too small to square without underflow, or so large that its square overflows, proves nothing)
+      const float bound = (gap > 1e-15f && gap < 1e18f) ? (gap * gap) * (1.0f - 0x1p-19f) : 0.f;
+      if (kth < FLT_MAX && kth < bound) {
+        done = true;
+        break;
+      }
+      if (reads + tests > budget) break;      // the finish is cheaper from here
     }
-    if (!done) {      // a far outlier: start over with a plain scan of the shape
+  }
+  // The exhaustive finish, by the whole wave for all its lanes that gave up.  Every lane of the wave arrives here, and `needy`,
+  // the choice between the two forms, `owner` and the row loops are wave-uniform (m and lo belong to the workgroup's shape).
+  //   few needy lanes   the QUERIES are broadcast.  The rows are the outer loop and the needy lanes the inner one: 4 x 64 rows
+  //                     are loaded once, coalesced, and serve every needy lane before the next load; m / 64 steps per needy
+  //                     lane, the insertions in the owner lane alone.
+  //   a crowded wave    the ROWS are broadcast: m steps, in each of them every needy lane tests the row against its own query
+  //                     and inserts into its own list -- as many tests per step, without the five broadcasts and the ballot
+  //                     per needy lane and with the insertions of a step side by side.
+  const unsigned long long needy = __ballot(!done);
+  if (needy && m > 0) {
+    float kd = FLT_MAX;      // this lane's k-th pair, what a candidate has to beat: kept beside the list for the broadcast
+    int ki = -1;
+    if (!done) {      // start over: a list that holds only rows of this scan cannot name a row twice
       scanned = 1;
+      tests += static_cast<unsigned>(m);
 #pragma unroll
       for (int t = 0; t < K; ++t) {
         bd[t] = FLT_MAX;
         bi[t] = -1;
       }
-      const float *src = source + static_cast<size_t>(lo) * 3;
-      for (int j = 0; j < m; ++j) {
-        ++tests;
-        consider(nsdp::sq_dist3(qx, qy, qz, src[j * 3 + 0], src[j * 3 + 1], src[j * 3 + 2]), j);
+    }
+    const float *src = source + static_cast<size_t>(lo) * 3;
+    // (K = 32 has this form alone, which costs any wave what one plain scan per lane did: with both forms that kernel needs
+    // 160 registers, not 121, a wave per SIMD less for every search, and with the other form alone a crowded wave takes twice
+    // the time of the plain scans)
+    if (K > kBothFormsMaxK || __popcll(needy) > kCrowd) {
+      // 64 rows one per lane, the next 64 in flight meanwhile (the last row of the shape again past its end; m >= 1 here: a
+      // shape without rows is a single cell, which shell 0 covers)
+      int j = min(lane, m - 1);
+      float px = src[j * 3 + 0], py = src[j * 3 + 1], pz = src[j * 3 + 2];
+      for (int jb = 0; jb < m; jb += kSearchLanes) {
+        j = min(jb + kSearchLanes + lane, m - 1);
+        const float nx = src[j * 3 + 0], ny = src[j * 3 + 1], nz = src[j * 3 + 2];
+        const int rows = min(kSearchLanes, m - jb);
+#pragma unroll 1
+        for (int r = 0; r < rows; ++r) {
+          const float rx = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(px), r));
+          const float ry = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(py), r));
+          const float rz = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(pz), r));
+          // (a lane that is not needy offers FLT_MAX, which enters no list: an empty slot is (FLT_MAX, -1))
+          consider(done ? FLT_MAX : nsdp::sq_dist3(qx, qy, qz, rx, ry, rz), jb + r);
+        }
+        px = nx; py = ny; pz = nz;
+      }
+    } else
+    for (int j0 = 0; j0 < m; j0 += 4 * kSearchLanes) {
+      float px[4], py[4], pz[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {      // 4 x 64 consecutive rows in flight (the last row of the shape again past its end)
+        const int j = min(j0 + u * kSearchLanes + lane, m - 1);
+        px[u] = src[j * 3 + 0]; py[u] = src[j * 3 + 1]; pz[u] = src[j * 3 + 2];
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int jb = j0 + u * kSearchLanes, j = jb + lane;
+        if (jb >= m) break;
+        for (unsigned long long left = needy; left; left &= left - 1) {
+          const int owner = __builtin_amdgcn_readfirstlane(__ffsll(left) - 1);
+          const float ox = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(qx), owner));
+          const float oy = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(qy), owner));
+          const float oz = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(qz), owner));
+          const float od = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(kd), owner));
+          const int oi = __builtin_amdgcn_readlane(ki, owner);
+          const float d = nsdp::sq_dist3(ox, oy, oz, px[u], py[u], pz[u]);
+          unsigned long long cand = __ballot(j < m && (d < od || (d == od && j < oi)));
+          if (cand) {
+            do {
+              const int from = __builtin_amdgcn_readfirstlane(__ffsll(cand) - 1);
+              cand &= cand - 1;
+              const float dc = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(d), from));
+              if (lane == owner) consider(dc, jb + from);
+            } while (cand);
+            if (lane == owner) {
+              kd = bd[0];
+              ki = bi[0];
+#pragma unroll
+              for (int t = 1; t < K; ++t) {
+                kd = (t == k - 1) ? bd[t] : kd;
+                ki = (t == k - 1) ? bi[t] : ki;
+              }
+            }
+          }
+        }
       }
     }
+  }
+  if (live) {
     int32_t *io = idx_all + out_row * k;
 #pragma unroll
     for (int t = 0; t < K; ++t)
