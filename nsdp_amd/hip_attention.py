@@ -1,6 +1,7 @@
 """Autograd wrappers of the fused vector-attention glue kernels (csrc/attention.hip)."""
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import os
 
@@ -58,10 +59,73 @@ FOLD_PRE_BWD = os.environ.get("NSDP_FOLD_PRE_BWD", "1") != "0"
 INVERSE_LISTS = os.environ.get("NSDP_INVERSE_LISTS", "1")         # "0": the global-atomic kernels (A/B knob)
 
 
-def _use_inverse(dt, qb, n, N, d):
+# Index sets over more than INVERT_WIDE_MIN_SOURCES - 1 source points get their lists from the many-workgroup build of
+# include/nsdp_scatter.h (csrc/invert_wide.hip: a counting sort in global memory, every list ascending, up to 2^20 sources and
+# 2^25 entries per shape) instead of nsdp_knn_invert's one workgroup per shape.  NSDP_INVERT_WIDE: "1" (default) = the wide build
+# above the sizes the old entry serves (which lifts the 8192-source bound of the list scatters: no fp32 atomics in the backward
+# of a large cloud), "0" = the old entry and its bounds everywhere (the A/B partner), "force" = the wide build wherever it
+# accepts the arguments.  Parsed as NSDP_KNN_GRID is; read when a call runs, so a captured graph keeps the kernels it was
+# captured with.
+INVERT_WIDE_MODES = ("0", "1", "force")
+INVERT_WIDE_MIN_SOURCES = 8193
+INVERT_WIDE_MAX_SOURCES, INVERT_WIDE_MAX_ENTRIES = 1 << 20, 1 << 25      # the limits of the entry
+INVERT_WIDE_TILE = 1024             # sources per workgroup of its scan (kScanTile of csrc/invert_wide.hip)
+INVERSE_MAX_SOURCES = 8192          # the bound of the list scatters without the wide build
+
+
+def _wide_mode(value, default: str = "1") -> str:
+    """NSDP_INVERT_WIDE's text -> "0" / "1" / "force" (the parsing of NSDP_KNN_GRID)."""
+    from .pointnet2_utils import _grid_mode
+    return _grid_mode(value, default)
+
+
+INVERT_WIDE = _wide_mode(os.environ.get("NSDP_INVERT_WIDE"))
+
+
+@contextlib.contextmanager
+def invert_wide_mode(mode):
+    """``with hip_attention.invert_wide_mode("0"): ...`` -- "0" / "1" / "force" (or False / True) inside the block, the previous
+    mode restored after it."""
+    global INVERT_WIDE
+    mode = {True: "1", False: "0"}.get(mode, mode)
+    if mode not in INVERT_WIDE_MODES:
+        raise ValueError(f"invert_wide_mode: one of {INVERT_WIDE_MODES}, got {mode!r}")
+    prev, INVERT_WIDE = INVERT_WIDE, mode
+    try:
+        yield
+    finally:
+        INVERT_WIDE = prev
+
+
+def _wide_accepts(B, E, N):
+    return 1 <= B <= 65535 and 1 <= E <= INVERT_WIDE_MAX_ENTRIES and 1 <= N <= INVERT_WIDE_MAX_SOURCES
+
+
+def _use_wide(B, E, N):
+    """Does ``inverse_lists`` take the many-workgroup build for B shapes of E entries over N sources?"""
+    if INVERT_WIDE == "0" or not _wide_accepts(B, E, N):
+        return False
+    return INVERT_WIDE == "force" or N >= INVERT_WIDE_MIN_SOURCES
+
+
+def max_list_sources():
+    """The most source points per shape a scatter through inverse lists is dispatched for."""
+    return INVERSE_MAX_SOURCES if INVERT_WIDE == "0" else INVERT_WIDE_MAX_SOURCES
+
+
+def lists_serve(B, E, N):
+    """Can ``inverse_lists`` build the lists of B shapes of E entries over N sources for a scatter?  Up to INVERSE_MAX_SOURCES
+    sources the one-workgroup entry does; above them only the wide build, within its limits (anything else keeps the atomics)."""
+    if N <= INVERSE_MAX_SOURCES:
+        return N > 0
+    return INVERT_WIDE != "0" and _wide_accepts(B, E, N)
+
+
+def _use_inverse(dt, qb, n, N, d, k=None, B=1):
     # (the decoder -- one query vector per shape, 57 344 entries over 100 anchors -- keeps its register table / scatter as a
     # GEMM: its lists are built by ONE workgroup per shape, 2 ms per step, more than the 0.4 ms the segment sum would save)
-    if qb or N > 8192 or INVERSE_LISTS == "0":
+    # k, B: the index set's neighbours per point and shapes; a caller that does not say is taken at k = 32, the searches' largest
+    if qb or INVERSE_LISTS == "0" or not lists_serve(B, n * (32 if k is None else k), N):
         return False
     table_fits_lds = N * d * 4 <= 110 * 1024 and n >= 4 * N            # (lds_table_fits of csrc/attention.hip)
     if table_fits_lds:
@@ -70,7 +134,8 @@ def _use_inverse(dt, qb, n, N, d):
 
 
 def inverse_lists(idx, N):
-    """(offsets [B,N+1], entries [B,E]) of idx [B,n,k] (nsdp_knn_invert), cached on the index tensor.
+    """(offsets [B,N+1], entries [B,E]) of idx [B,n,k] (nsdp_knn_invert, or nsdp_knn_invert_wide above 8192 sources: see
+    INVERT_WIDE), cached on the index tensor.
     The cache is keyed by the CONTENTS' identity as far as PyTorch exposes it -- (N, storage pointer, version counter): an
     index buffer that is refilled in place (`copy_` into a static input of a captured step) gets new lists.  While a stream
     capture is running the cache is neither read nor written: the list build must be a node of the graph (a replay sees
@@ -90,8 +155,19 @@ def inverse_lists(idx, N):
     offsets = torch.empty((B, N + 1), dtype=torch.int32, device=idx.device)
     entries = torch.empty((B, E), dtype=torch.int32, device=idx.device)
     with on_device(idx):
-        check(lib().nsdp_knn_invert(iptr(idx, "idx"), _ci(B), _ci(E), _ci(N), iptr(offsets), iptr(entries), stream_ptr()),
-              "nsdp_knn_invert")
+        if idx.is_cuda and _use_wide(B, E, N):
+            L = lib()
+            L.nsdp_knn_invert_wide_workspace_bytes.restype = ctypes.c_size_t
+            need = int(L.nsdp_knn_invert_wide_workspace_bytes(_ci(B), _ci(E), _ci(N)))
+            # (allocated per call and dropped behind the launch, also inside a capture: the allocator hands the block on in
+            # stream order, and a graph's private pool keeps it for the replays)
+            ws = torch.empty((need,), dtype=torch.uint8, device=idx.device)
+            check(L.nsdp_knn_invert_wide(iptr(idx, "idx"), _ci(B), _ci(E), _ci(N), ctypes.c_void_p(ws.data_ptr()), iptr(offsets),
+                                         iptr(entries), stream_ptr()), "nsdp_knn_invert_wide")
+            del ws
+        else:
+            check(lib().nsdp_knn_invert(iptr(idx, "idx"), _ci(B), _ci(E), _ci(N), iptr(offsets), iptr(entries), stream_ptr()),
+                  "nsdp_knn_invert")
     cache[key] = (offsets, entries)
     return offsets, entries
 
@@ -202,7 +278,7 @@ class _AttnPre(torch.autograd.Function):
         fused = link is not None and link.fused
         if link is not None and not fused:
             acc, link.dpos = link.dpos, None
-        if acc is None and _use_inverse(dt, qb, n, N, d):
+        if acc is None and _use_inverse(dt, qb, n, N, d, k, B):
             # dq from a pure stream over du, dkf = -scatter(du) as a gather-reduce over the inverse neighbour lists
             fold = fused and not qb and FOLD_PRE_BWD and link.dvf.dtype is torch.float32 and link.dy.dtype is dt
             with on_device(du):
@@ -303,7 +379,7 @@ class _AttnPost(torch.autograd.Function):
         link = ctx.link
         qb = bool(link.qb) if link is not None else False
         # (a per-shape-query block has no inverse lists -- backward_lists(qb=True) builds none -- and must not build them here)
-        inverse = (vf is not None and not onehot and a_g is None and _use_inverse(dt, qb, n, N, d)
+        inverse = (vf is not None and not onehot and a_g is None and _use_inverse(dt, qb, n, N, d, k, B)
                    and (ctx.inv is not None or not qb))
         dvf = torch.empty((B, N, d), dtype=torch.float32, device=dev) if (vf is not None and not onehot and not inverse) else None
         da_g = torch.empty((B, d), dtype=torch.float32, device=dev) if a_g is not None else None
@@ -374,7 +450,7 @@ def backward_lists(idx, n, N, d, qb=False):
     """The inverse neighbour lists the backward pass of an attention block over this index set will want, or None.
     Built in the FORWARD pass (once per index set: the cache lives on the index tensor object, which the backward pass
     no longer sees) and handed to attn_pre / attn_post as ``inv``."""
-    if not torch.is_grad_enabled() or not _use_inverse(torch.float32, qb, n, N, d):
+    if not torch.is_grad_enabled() or not _use_inverse(torch.float32, qb, n, N, d, idx.shape[-1], idx.shape[0]):
         return None
     return inverse_lists(idx, N)
 

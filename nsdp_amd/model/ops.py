@@ -45,7 +45,7 @@ def attention_lists(idx: torch.Tensor, n: int, N: int, d: int, per_shape_query: 
     """The inverse neighbour lists the BACKWARD pass of a d-wide attention block over ``idx`` [B,n,k] (sources: N) scatters
     through (hip_attention._use_inverse decides whether it uses any), or None -- for callers that prepare a block's geometry
     outside its forward pass, where grad mode says nothing."""
-    if not hip_attention._use_inverse(torch.float32, per_shape_query, n, N, d):
+    if not hip_attention._use_inverse(torch.float32, per_shape_query, n, N, d, idx.shape[-1], idx.shape[0]):
         return None
     return hip_attention.inverse_lists(idx, N)
 
@@ -120,9 +120,9 @@ def _pyramid_levels(levels, cur, npoints, ks, dims):
         lv = {"fps_idx": fps_idx, "new_xyz": new_xyz, "sa_idx": sa_idx, "blk_idx": blk_idx}
         if dims is not None and PYRAMID_LISTS:
             d = dims[len(levels)]
-            if hip_attention._use_inverse(torch.float32, False, n_new, cur.shape[1], d):
+            if hip_attention._use_inverse(torch.float32, False, n_new, cur.shape[1], d, k_sa, cur.shape[0]):
                 lv["sa_inv"] = hip_attention.inverse_lists(sa_idx, cur.shape[1])
-            if blk_idx is not None and hip_attention._use_inverse(torch.float32, False, n_new, n_new, d):
+            if blk_idx is not None and hip_attention._use_inverse(torch.float32, False, n_new, n_new, d, k_blk, cur.shape[0]):
                 lv["blk_inv"] = hip_attention.inverse_lists(blk_idx, n_new)
         levels.append(lv)
         cur = new_xyz

@@ -475,10 +475,12 @@ def scatter_add_rows(grad_out: torch.Tensor, idx: torch.Tensor, N: int) -> torch
     # float4 rows for the list kernel; through the atomic kernel those three-float rows made the whole step depend on the order
     # in which atomics retire (two eager runs of one FlowArbitrary step differed in 1589 of 1813 tensors).  _SCATTER_DETERMINISTIC
     # (default on) also takes the lists below the row count where one atomic launch is faster.
-    if (_SCATTER_INVERSE and 1 <= C <= 256 and 0 < int(N) <= 8192 and S <= 64 * int(N) and S > 0
+    # Above 8192 source points the lists come from the many-workgroup build, within its limits (hip_attention.lists_serve; the
+    # knob INVERT_WIDE at "0" keeps the bound); what it does not accept keeps the atomic kernel.
+    from . import hip_attention
+    if (_SCATTER_INVERSE and 1 <= C <= 256 and S > 0 and hip_attention.lists_serve(B, S, int(N)) and S <= 64 * int(N)
             and (B * S >= _SCATTER_INVERSE_MIN_ROWS or _SCATTER_DETERMINISTIC)
             and grad_out.is_cuda and grad_out.dtype is torch.float32 and grad_out.is_contiguous()):
-        from . import hip_attention
         if C % 4:
             padded = torch.nn.functional.pad(grad_out, (0, 4 - C % 4))
             return hip_attention.segment_sum(padded, idx, int(N), 1.0)[:, :, :C].contiguous()

@@ -181,6 +181,8 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=27)
     ap.add_argument("--synthetic", type=int, default=4, help="procedural batches per epoch (no dataset readers yet)")
     ap.add_argument("--batch", type=int, default=8, help="shapes per batch = per GPU and step (the global batch is this x --gpus)")
+    ap.add_argument("--surface", type=int, default=2048, help="surface samples per shape of the procedural batches (default 2048)")
+    ap.add_argument("--queries", type=int, default=8192, help="query points per shape of the procedural batches (default 8192)")
     ap.add_argument("--epochs", type=int, default=None)
     ap.add_argument("--graph", action="store_true",
                     help="capture the train step once and replay it (nsdp_amd.graph_step.GraphedTrainOnBatch): batches of "
@@ -191,6 +193,8 @@ def main(argv=None):
                          "the ranks are launched here; under torchrun (RANK / WORLD_SIZE set) this process is one of them")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend of the data-parallel job (nccl = RCCL)")
     args = ap.parse_args(argv)
+    if args.surface < 1 or args.queries < 1:
+        sys.exit(f"nsdp_amd.train: --surface {args.surface} and --queries {args.queries} must be positive")
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if args.gpus is not None and args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return launch_ranks(args.gpus, argv)
@@ -234,8 +238,9 @@ def main(argv=None):
         from .graph_step import GraphedTrainOnBatch
         train_fn = GraphedTrainOnBatch(train_fn, reducer=dp.reducer if dp is not None else None)
     # (one loader of world x synthetic batches: every rank builds the same list and takes its share, DataParallel.shard)
-    train = SyntheticLoader(args.seed, args.synthetic * world, args.batch)
-    val = SyntheticLoader(args.seed + 10000, max(1, args.synthetic // 4) * world, args.batch)
+    train = SyntheticLoader(args.seed, args.synthetic * world, args.batch, n_surf=args.surface, n_query=args.queries)
+    val = SyntheticLoader(args.seed + 10000, max(1, args.synthetic // 4) * world, args.batch, n_surf=args.surface,
+                          n_query=args.queries)
     fit(model, (train_fn, val_fn), lr_scheduler, optimizer, train, val, config, args.experiment_directory, args, device,
         log=say, dp=dp)
     if dp is not None:
