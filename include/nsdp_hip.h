@@ -522,6 +522,20 @@ int nsdp_linear_wgrad_k4_bf16(const void *dY, const float *X, const void *mask, 
  * :290-308 and model/decoder/blocks.py:72-91.  Channels-last fp32, d <= 256:
  *   q (B,n,d) per-centre queries;  kf, vf (B,N,d) projected source features;  idx (B,n,k) i32 neighbours
  *   pos, u, a (B,n,k,d) per-(centre,neighbour) tensors;  a_g, v_g (B,d) optional global token (decoder).
+ *
+ * Accuracy contract (tests/attention_ref.py holds the formulas, tests/test_attention_forms_gpu.py every
+ * dispatch form to them): each output element is within a few first-order rounding envelopes of the exact result of the
+ * inputs -- no absolute floor.  u = 2^-24, u_s = u (fp32 storage) or 2^-9 (bf16), w_j = exp(a_j - lse), s_j the values,
+ * yb = sum_j w_j s_j, c_j = 3 + |a_j - lse| + |lse| + |a_j|:
+ *   dpos_j: u |dy| w_j c_j + u_s |dpos_j|
+ *   da_j:   u |dy| w_j (c_j |s_j - yb| + |s_j| + |yb| + sum_i w_i |s_i|) + u_s |dy| w_j (|y| + |residual|) + u_s |da_j|
+ *   y:      u sum_j w_j |s_j| c_j + u_s (|y| + |residual|);      u: u (|q - k| + |u|) + u_s |u|
+ *   sums (dvf, dkf, dq, da_g, dv_g) of L addends: the addends' envelopes + L u sum |addend|, in any order.
+ * Two sensitivities belong to the formulation: the weights are recomputed from the fp32 lse (|lse| u relative: a common
+ * logit offset of 1000 costs 3e-5), and the attention output is recovered as yb = y - residual from the stored y (its
+ * rounding enters da at the scale |y| + |residual|).  __expf returns zero below 2^-126: a weight more than 86.6 under the
+ * lse is off by up to 2^-126 absolutely.  PRECONDITION: finite logits (a leading -inf logit makes the online step evaluate
+ * exp(-inf - -inf)).
  * -------------------------------------------------------------------------------------------- */
 
 /* u = q[:, :, None] - kf[idx] + pos;  q_per_shape = 1: q is (B,1,d), one query vector per shape shared
