@@ -493,6 +493,80 @@ def scatter_add_rows(grad_out: torch.Tensor, idx: torch.Tensor, N: int) -> torch
     return out
 
 
+# User-handle drags (include/nsdp_handles.h, csrc/handles.hip): the bounding box of a cloud, and the handle rule + dragged target
+# + columns 3..6 of the deformation network's input rows, with the drag parameters in device memory (nsdp_amd.edit).
+HANDLE_PARTS = ("head", "tail", "frontleftfoot", "frontrightfoot", "behindleftfoot", "behindrightfoot")      # NSDP_HANDLE_* order
+HANDLE_PARAM_WORDS = 8
+HANDLE_MAX_POINTS = 1 << 20
+
+
+def _points3(what, t):
+    if not torch.is_tensor(t) or t.dim() != 3 or t.shape[2] != 3:
+        raise _lib.NsdpHipError(f"{what} must be (B, n, 3), got {tuple(t.shape) if torch.is_tensor(t) else type(t).__name__}")
+
+
+def _bytes_ptr(t, name, shape):
+    """A (B,n) mask or flag tensor of one-byte elements (uint8 or bool) as a pointer; None -> null."""
+    if t is None:
+        return ctypes.c_void_p(0)
+    if not torch.is_tensor(t) or not t.is_cuda:
+        raise _lib.NsdpHipError(f"{name} must be a GPU tensor (CPU not supported, no fallback)")
+    if t.dtype not in (torch.uint8, torch.bool) or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise _lib.NsdpHipError(f"{name} must be a contiguous uint8 / bool tensor of shape {tuple(shape)}, got {t.dtype} "
+                                f"{tuple(t.shape)}")
+    return ctypes.c_void_p(t.data_ptr())
+
+
+def handle_bounds(cano: torch.Tensor, workspace=None, out=None) -> torch.Tensor:
+    """Per-shape bounding box (nsdp_handle_bounds): cano (B,n,3) fp32 -> (B,6) fp32, min xyz then max xyz, the exact extremes
+    (-0.0 sorts below +0.0).  ``workspace``: a buffer of the caller's, else allocated here; ``out``: a (B,6) buffer."""
+    with on_device(cano):
+        _points3("cano", cano)
+        B, n = int(cano.shape[0]), int(cano.shape[1])
+        fn = lib().nsdp_handle_bounds_workspace_bytes
+        fn.restype = ctypes.c_size_t
+        need = int(fn(_c_int(B), _c_int(n)))
+        if need == 0:
+            raise _lib.NsdpHipError(f"handle_bounds: B={B} shapes of n={n} points outside 1..65535 x 1..{HANDLE_MAX_POINTS}")
+        if workspace is None:
+            workspace = torch.empty((need // 4,), dtype=torch.int32, device=cano.device)
+        elif not (workspace.is_cuda and workspace.is_contiguous() and workspace.numel() * workspace.element_size() >= need):
+            raise _lib.NsdpHipError(f"handle_bounds: the workspace must be a contiguous GPU tensor of at least {need} bytes")
+        bounds = torch.empty((B, 6), dtype=torch.float32, device=cano.device) if out is None else out
+        if tuple(bounds.shape) != (B, 6):
+            raise _lib.NsdpHipError(f"handle_bounds: out must be ({B}, 6), got {tuple(bounds.shape)}")
+        check(lib().nsdp_handle_bounds(fptr(cano, "cano"), _c_int(B), _c_int(n), optptr(workspace), fptr(bounds, "bounds"),
+                                       stream_ptr()), "nsdp_handle_bounds")
+    return bounds
+
+
+def handle_rows(cano, src: torch.Tensor, bounds, params: torch.Tensor, rows: torch.Tensor, handle_mask=None, move_mask=None,
+                tgt=None, handle_out=None, move_out=None) -> torch.Tensor:
+    """One drag written into the deformation network's input rows (nsdp_handle_rows): columns 3..6 of ``rows`` (B,n,7) become
+    [handle * tgt | handle] with tgt = src + d * move; columns 0..2 are never written.  ``params`` (B,8) int32 on the device:
+    {part, cliptail, partial_range, dx, dy, dz, 0, 0} (the floats by their bits).  ``handle_mask`` / ``move_mask`` (B,n) uint8 or
+    bool, together: they replace the rule (cano and bounds may then be None).  ``tgt`` (B,n,3), ``handle_out`` / ``move_out``
+    (B,n) uint8: optional outputs, buffers of the caller's.  Returns ``rows``."""
+    with on_device(src):
+        _points3("src", src)
+        B, n = int(src.shape[0]), int(src.shape[1])
+        if cano is not None:
+            _points3("cano", cano)
+        if tuple(rows.shape) != (B, n, 7) or (cano is not None and cano.shape != src.shape) or (tgt is not None and tgt.shape != src.shape):
+            raise _lib.NsdpHipError(f"handle_rows: src ({B},{n},3) goes with cano and tgt of that shape and rows ({B},{n},7), got "
+                                    f"rows {tuple(rows.shape)}")
+        if tuple(params.shape) != (B, HANDLE_PARAM_WORDS) or (bounds is not None and tuple(bounds.shape) != (B, 6)):
+            raise _lib.NsdpHipError(f"handle_rows: params must be ({B}, {HANDLE_PARAM_WORDS}) int32 and bounds ({B}, 6)")
+        check(lib().nsdp_handle_rows(optptr(None) if cano is None else fptr(cano, "cano"), fptr(src, "src"),
+                                     optptr(None) if bounds is None else fptr(bounds, "bounds"), iptr(params, "params"),
+                                     _bytes_ptr(handle_mask, "handle_mask", (B, n)), _bytes_ptr(move_mask, "move_mask", (B, n)),
+                                     _c_int(B), _c_int(n), fptr(rows, "rows"),
+                                     optptr(None) if tgt is None else fptr(tgt, "tgt"),
+                                     _bytes_ptr(handle_out, "handle_out", (B, n)), _bytes_ptr(move_out, "move_out", (B, n)),
+                                     stream_ptr()), "nsdp_handle_rows")
+    return rows
+
+
 # ------------------------------------------------------------------------------------------------
 # autograd Functions with the reference's names and signatures
 # ------------------------------------------------------------------------------------------------

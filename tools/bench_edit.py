@@ -1,0 +1,155 @@
+"""An editing session's drag against the call it replaces, in one process on one GPU (profiles/edit_session.txt).
+
+    python tools/bench_edit.py [--sizes 5000,25000,100000] [--reps 5] [--batch 1]
+
+The tosca user-handle configuration's model (FlowArbitrary, npoints_per_layer [5000, 500, 100]; procedural weights), the cloud
+= the vertex set (the reference's user-handle data set), one mesh of N uniform vertices per size.  Per size one JSON line with the
+median and min-max in ms over ``reps`` interleaved repetitions (session eager, session replayed, full call eager, full call
+replayed, session eager, ...), each a window of several calls between two HIP events, after untimed warm-up calls of every
+variant; every drag of a window has another translation:
+
+    drag_eager_ms     EditSession.drag, op by op;
+    drag_graph_ms     EditSession(graph=True).drag: parameter copy + replay;
+    full_eager_ms     the parent's path: test_on_batch_with_arbitrary on the data_dict the same drag stands for (the dict is built
+                      before the window; building it is not in the time);
+    full_graph_ms     ... through query_sharded(test_on_batch_with_arbitrary, QueryShards(0, 1), graph=True): copy of the inputs +
+                      replay;
+    open_ms           EditSession.reopen(): network 1, network 2's index sets, the bounds (windows of one);
+    bounds_ms, rows_ms   nsdp_handle_bounds and nsdp_handle_rows alone (windows of 200 launches);
+    equal             the session's predictions, eager and replayed, are bit-equal to the full call's.
+
+The ratios ``full_eager / drag_eager`` and ``full_graph / drag_graph`` are reported as they come out; nothing is tuned to them.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from nsdp_amd import pointnet2_utils as pu, synth                                  # noqa: E402
+from nsdp_amd.config import default_config                                         # noqa: E402
+from nsdp_amd.edit import EditSession, HandleSpec, pack_params, reference_data_dict  # noqa: E402
+from nsdp_amd.model import build_model                                             # noqa: E402
+from nsdp_amd.model.flow_arbitrary import test_on_batch_with_arbitrary             # noqa: E402
+from nsdp_amd.query_shard import QueryShards, query_sharded                        # noqa: E402
+
+SPEC = HandleSpec("head", (-0.15, -0.2, -0.2), 0.1, False)      # config/tosca/head.yaml's drag
+KEYS = ("verts_tgt_pred", "surface_samples_tgt_pred")
+KERNEL_WINDOW = 200
+
+
+def window(fn, n):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    a.record()
+    for i in range(n):
+        fn(i)
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / n
+
+
+def stats(xs):
+    return {"median": round(statistics.median(xs), 4), "min": round(min(xs), 4), "max": round(max(xs), 4)}
+
+
+def bench_size(model, N, batch, reps, dev):
+    verts = torch.from_numpy(synth.uniform(1000, "mesh_verts", (batch, N, 3), -0.5, 0.5)).to(dev)
+    calls = 20 if N <= 25000 else 10
+
+    def translation(i):
+        return tuple(v * (1.0 + 0.01 * (i % 7)) for v in SPEC.translation)
+
+    eager, graphed = EditSession(model, verts), EditSession(model, verts, graph=True)
+    full_graph = query_sharded(test_on_batch_with_arbitrary, QueryShards(0, 1), graph=True)
+    # the data_dicts of the drags of a window, built with torch ahead of it (seven distinct translations)
+    dicts = [reference_data_dict(verts, None, HandleSpec(SPEC.part, translation(i), SPEC.partial_range, SPEC.cliptail))
+             for i in range(7)]
+    dicts = [{k: d[k] for k in ("surface_samples_inputs", "verts_src")} for d in dicts]
+    variants = {
+        "drag_eager_ms": lambda i: eager.drag(SPEC.part, translation(i), clone=False),
+        "drag_graph_ms": lambda i: graphed.drag(SPEC.part, translation(i), clone=False),
+        "full_eager_ms": lambda i: test_on_batch_with_arbitrary(model, dict(dicts[i % 7]), None),
+        "full_graph_ms": lambda i: full_graph(model, dict(dicts[i % 7]), None),
+    }
+    # results first: the same drag through all four
+    want = test_on_batch_with_arbitrary(model, dict(dicts[3]), None)[1]
+    got = [eager.drag(SPEC.part, translation(3)), graphed.drag(SPEC.part, translation(3)), full_graph(model, dict(dicts[3]), None)[1]]
+    equal = all(torch.equal(g[k], want[k]) for g in got for k in KEYS)
+    for fn in variants.values():      # warm-up of every variant (the captures happened above)
+        for i in range(3):
+            fn(i)
+    times = {k: [] for k in variants}
+    times["open_ms"] = []
+    for _ in range(reps):
+        for k, fn in variants.items():
+            times[k].append(window(fn, calls))
+        times["open_ms"].append(window(lambda i: eager.reopen(), 1))
+    # the two kernels alone
+    params = torch.from_numpy(pack_params(batch, SPEC.part, SPEC.translation, SPEC.partial_range, SPEC.cliptail)).to(dev)
+    rows = torch.empty(batch, N, 7, device=dev)
+    tgt = torch.empty(batch, N, 3, device=dev)
+    flags = torch.empty(batch, N, dtype=torch.uint8, device=dev)
+    bounds = pu.handle_bounds(verts)
+    ws = torch.empty(1 << 16, dtype=torch.int32, device=dev)
+    kernels = {"bounds_ms": lambda i: pu.handle_bounds(verts, workspace=ws, out=bounds),
+               "rows_ms": lambda i: pu.handle_rows(verts, verts, bounds, params, rows, tgt=tgt, handle_out=flags)}
+    for fn in kernels.values():
+        fn(0)
+    for k in kernels:
+        times[k] = []
+    for _ in range(reps):
+        for k, fn in kernels.items():
+            times[k].append(window(fn, KERNEL_WINDOW))
+    pu.check_fps_cluster()
+    line = {"vertices": N, "batch": batch, "calls_per_window": calls, "reps": reps,
+            "handle_points": int(eager.drag(SPEC.part, SPEC.translation)["cano_handle_sample_idx"].sum()),
+            **{k: stats(v) for k, v in times.items()}, "equal": bool(equal),
+            "graph_nodes": {"session": graphed._steps[(False, False)].info, "full_call": full_graph._step.info},
+            "replays": graphed.replays}
+    med = {k: statistics.median(v) for k, v in times.items()}
+    line["full_eager_over_drag_eager"] = round(med["full_eager_ms"] / med["drag_eager_ms"], 3)
+    line["full_graph_over_drag_graph"] = round(med["full_graph_ms"] / med["drag_graph_ms"], 3)
+    line["full_eager_over_drag_graph"] = round(med["full_eager_ms"] / med["drag_graph_ms"], 3)
+    for s in (eager, graphed, full_graph):
+        s.close()
+    return line
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
+    ap.add_argument("--sizes", default="5000,25000,100000")
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--batch", type=int, default=1)
+    args = ap.parse_args(argv)
+    if not torch.cuda.is_available():
+        sys.exit("tools/bench_edit.py: needs a GPU (nothing here is a CPU measurement)")
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(0)
+    config = default_config("arbitrary")      # the tosca user-handle configs' model block
+    model = build_model(config, device="cpu")[0]
+    state = synth.procedural_state_dict(model.state_dict(), 2048)
+    model.load_state_dict({k: torch.from_numpy(v) for k, v in state.items()})
+    model.to(dev).eval()
+    print(json.dumps({"tool": "bench_edit", "device": torch.cuda.get_device_name(0), "model": config["model"]}), flush=True)
+    lines = []
+    with torch.no_grad():
+        for N in (int(s) for s in args.sizes.split(",")):
+            lines.append(bench_size(model, N, args.batch, args.reps, dev))
+            print(json.dumps(lines[-1]), flush=True)
+    print(f"{'vertices':>9} {'drag eager':>11} {'drag graph':>11} {'full eager':>11} {'full graph':>11} {'open':>9} "
+          f"{'bounds':>8} {'rows':>8}  full/drag eager, graph   equal   (ms, medians)")
+    for ln in lines:
+        m = {k: ln[k]["median"] for k in ln if k.endswith("_ms")}
+        print(f"{ln['vertices']:>9} {m['drag_eager_ms']:>11.3f} {m['drag_graph_ms']:>11.3f} {m['full_eager_ms']:>11.3f} "
+              f"{m['full_graph_ms']:>11.3f} {m['open_ms']:>9.3f} {m['bounds_ms']:>8.4f} {m['rows_ms']:>8.4f}  "
+              f"{ln['full_eager_over_drag_eager']:>6.2f} {ln['full_graph_over_drag_graph']:>6.2f}            {ln['equal']}")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
