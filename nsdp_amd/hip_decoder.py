@@ -259,7 +259,11 @@ def decoder_forward_ragged(dec, points, encoding: dict, out=None):
         elif tuple(out.shape) != (cap, OUT):
             raise _lib.NsdpHipError(f"ragged decode: out must be [{cap}, {OUT}], got {tuple(out.shape)}")
         if cap:
-            idx = pointnet2_utils.knn_ragged(xyz_q, points.offsets, anchors, ct.nneigh)      # [cap,k] int32
+            idx = encoding.get("query_idx") if encoding.get("query_points") is points else None      # (searched ahead: Deformation_Networks.ragged_geometry)
+            if idx is None:
+                idx = pointnet2_utils.knn_ragged(xyz_q, points.offsets, anchors, ct.nneigh)      # [cap,k] int32
+            elif tuple(idx.shape) != (cap, ct.nneigh):
+                raise _lib.NsdpHipError(f"ragged decode: cached query_idx must be [{cap}, {ct.nneigh}], got {tuple(idx.shape)}")
             qk, vtab, a_g, v_g = _shape_tables(pack, z, feats)
             name = "nsdp_decoder_fused_fwd_bf16_ragged" if bf16 else "nsdp_decoder_fused_fwd_ragged"
             _lib.check(getattr(_lib.lib(), name)(

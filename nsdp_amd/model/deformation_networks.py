@@ -58,20 +58,56 @@ class Deformation_Networks(nn.Module):
         g["query_points"] = points
         return g
 
-    def encode(self, surface_samples_inputs, queries=None, geometry=None):
+    @torch.no_grad()
+    def ragged_geometry(self, points, surface_samples_inputs):
+        """geometry() for a PACKED surface cloud (a RaggedPoints of [total, C] rows): the encoder's index sets
+        (PointTransformerEncoder.ragged_geometry) and, for ``points`` -- a RaggedPoints of queries -- each query's nearest anchors
+        (``query_idx`` [cap, k], ``query_points`` = points).  ``encode(cloud, ragged_geometry=g)`` then searches nothing, and
+        ``decode(points, encoding)`` takes the cached neighbours when ``points`` is the very object given here.  The cloud's
+        coordinates (columns 0:3) must be the ones these sets were made from; its other columns may change between calls."""
+        if not isinstance(surface_samples_inputs, RaggedPoints) or not isinstance(points, RaggedPoints):
+            raise ValueError("ragged_geometry(): a RaggedPoints of queries and a RaggedPoints surface cloud (geometry() takes the "
+                             "rectangular ones)")
+        why = self.ragged_surface_refusal()
+        if why is not None:
+            raise ValueError("ragged surface cloud refused: " + why)
+        cloud = surface_samples_inputs.columns(0, 3) if self.no_input_corr else surface_samples_inputs
+        g = {"encoder": self.encoder.ragged_geometry(cloud)}
+        g.update(self.query_geometry_ragged(points, g["encoder"]["anchors"]))
+        return g
+
+    def query_geometry_ragged(self, points, anchors):
+        """The decoder side of ragged_geometry() alone: packed queries against anchors [B, A, 3] -> ``query_idx`` [cap, k]
+        (hip_decoder.decoder_forward_ragged's search, on its operands) and ``query_points``."""
+        from .. import pointnet2_utils as pu
+        if points.batch != anchors.shape[0]:
+            raise ValueError(f"ragged_geometry(): {points.batch} shapes of queries against anchors of {anchors.shape[0]}")
+        xyz_q = points.packed.contiguous().float()
+        idx = pu.knn_ragged(xyz_q, points.offsets, anchors.contiguous().float(), self.decoder.ct1.nneigh)
+        return {"query_idx": idx, "query_points": points}
+
+    def encode(self, surface_samples_inputs, queries=None, geometry=None, ragged_geometry=None):
         """The encoding {'z', 'anchors', 'anchor_feats'} of a surface cloud -- the half of forward() that does not depend on
         the query points.  Callers that decode several query sets against ONE cloud (FlowArbitrary, the dense-inference step
         functions) encode once and call decode() per set; the reference re-runs the whole module each time.
         ``queries``: the points decode() will be called with next -- the decoder's anchor-only work is then launched beside the
         encoder's forward chain (CrossTransformerDecoder.prefetch, NSDP_DECODER_PREFETCH=0 switches it off).
         ``surface_samples_inputs`` may be a RaggedPoints of [total, C] rows (clouds of different sample counts, nsdp_amd.ragged):
-        inference only, refused with its reason where it cannot run (ragged_surface_refusal)."""
+        inference only, refused with its reason where it cannot run (ragged_surface_refusal).  ``ragged_geometry``: the index
+        sets of that packed cloud computed ahead (ragged_geometry()); the encoding then carries ``query_idx`` / ``query_points``."""
         if isinstance(surface_samples_inputs, RaggedPoints):
             why = self.ragged_surface_refusal(geometry)
             if why is not None:
                 raise ValueError("ragged surface cloud refused: " + why)
+            if ragged_geometry is not None:
+                cloud = surface_samples_inputs.columns(0, 3) if self.no_input_corr else surface_samples_inputs
+                enc = self.encoder._forward_ragged(cloud, ragged_geometry=ragged_geometry["encoder"])
+                enc["query_idx"], enc["query_points"] = ragged_geometry.get("query_idx"), ragged_geometry.get("query_points")
+                return enc
             surface_samples_inputs.counts      # (read back once, here: a column view made below shares the host copy)
             return self.encoder(surface_samples_inputs.columns(0, 3) if self.no_input_corr else surface_samples_inputs)
+        if ragged_geometry is not None:
+            raise ValueError("ragged_geometry= goes with a packed surface cloud (a RaggedPoints); geometry= with a rectangular one")
         x = surface_samples_inputs[:, :, 0:3].contiguous() if self.no_input_corr else surface_samples_inputs
         if geometry is not None:
             enc = self.encoder(x, geometry=geometry["encoder"])

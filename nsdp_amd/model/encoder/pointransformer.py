@@ -126,17 +126,14 @@ class PointTransformerEncoder(nn.Module):
             return f"packed rows must be float32, got {cloud.packed.dtype}"
         return None
 
-    def _forward_ragged(self, cloud):
-        """forward() for B clouds of different sample counts, packed: transformer_begin and the first set abstraction run on the
-        tight rows as ONE shape [1,total,.] with per-shape index sets (ops.geometry_pyramid_ragged: every neighbour of a row is a
-        row of its own shape), the abstraction's output is [B,n1,d], and the rest is the rectangular code.  Eval-mode BatchNorm
-        is a per-row affine map, so every shape gets what its own batch-1 call gives it."""
+    def _ragged_counts(self, cloud):
+        """The host counts of a packed cloud this encoder can take (ValueError with the reason otherwise)."""
         why = self.ragged_refusal(cloud)
         if why is not None:
             raise ValueError("ragged surface cloud refused: " + why)
         counts = cloud.counts                      # (host counts: read back once if the set was built from device offsets alone)
         npoints, ks, _ = self._pyramid_args()
-        tb, B, total = self.transformer_begin, cloud.batch, sum(counts)
+        tb = self.transformer_begin
         for b, n in enumerate(counts):
             if n == 0:
                 raise ValueError(f"ragged surface cloud: shape {b} is empty (0 samples)")
@@ -148,10 +145,62 @@ class PointTransformerEncoder(nn.Module):
                     raise ValueError(f"ragged surface cloud: shape {b} has {n} samples, fewer than the {k} neighbours of the {what}")
         if tb.group_all:
             raise ValueError("ragged surface cloud refused: a first block that attends to the whole cloud (group_all) has no ragged form")
+        return counts
+
+    @torch.no_grad()
+    def ragged_geometry(self, cloud):
+        """Everything _forward_ragged derives from the COORDINATES of a packed cloud alone, computed on the current stream and
+        joined: ``begin_idx`` and ``levels`` of ops.geometry_pyramid_ragged, the final blocks' shared ``final_idx`` /
+        ``final_rel`` (None where no set is shared), the ``anchors`` [B,n_last,3], and the host's ``counts`` / ``total``.
+        ``_forward_ragged(cloud, ragged_geometry=)`` takes it instead of searching -- for the SAME coordinates in the same rows;
+        only the feature columns may differ (nsdp_amd.edit.RaggedEditSession: a drag changes columns 3:7)."""
+        counts = self._ragged_counts(cloud)
+        npoints, ks, _ = self._pyramid_args()
+        tb, B, total = self.transformer_begin, cloud.batch, sum(counts)
+        rows = cloud.packed[:total]
+        coords = rows[:, :3].contiguous() if self.has_features else rows.contiguous()
+        begin_idx, levels, join = ops.geometry_pyramid_ragged(coords, cloud.offsets, max(counts), tb.k, npoints, ks)
+        join()
+        last = levels[-1]["new_xyz"].view(B, npoints[-1], 3)
+        g = {"begin_idx": begin_idx, "levels": levels, "anchors": last, "counts": tuple(counts), "total": total,
+             "final_idx": None, "final_rel": None}
+        # the set _below_begin shares among the final blocks, made the way it makes it
+        same = len({(blk.group_all, blk.k) for blk in self.final_transformers}) == 1
+        blk = next((b for b in self.final_transformers if same or not b.group_all), None)
+        if blk is not None:
+            n = last.shape[1]
+            if blk.group_all:
+                g["final_idx"] = torch.arange(n, device=last.device, dtype=torch.int32).view(1, 1, n).expand(B, n, n).contiguous()
+            else:
+                g["final_idx"] = ops.knn_indices(last, last, blk.k)
+            g["final_rel"] = ops.relative_coords(last, last, g["final_idx"])
+        return g
+
+    def _forward_ragged(self, cloud, ragged_geometry=None):
+        """forward() for B clouds of different sample counts, packed: transformer_begin and the first set abstraction run on the
+        tight rows as ONE shape [1,total,.] with per-shape index sets (ops.geometry_pyramid_ragged: every neighbour of a row is a
+        row of its own shape), the abstraction's output is [B,n1,d], and the rest is the rectangular code.  Eval-mode BatchNorm
+        is a per-row affine map, so every shape gets what its own batch-1 call gives it.  ``ragged_geometry``: the index sets of
+        these coordinates, computed ahead (ragged_geometry()); nothing is searched then and the host reads nothing back."""
+        npoints, ks, _ = self._pyramid_args()
+        tb, B = self.transformer_begin, cloud.batch
+        if ragged_geometry is not None:
+            why = self.ragged_refusal(cloud)
+            if why is not None:
+                raise ValueError("ragged surface cloud refused: " + why)
+            total = ragged_geometry["total"]
+            if len(ragged_geometry["counts"]) != B or total > cloud.capacity:
+                raise ValueError(f"ragged surface cloud: index sets of {len(ragged_geometry['counts'])} shapes in {total} rows "
+                                 f"against a cloud of {B} shapes in {cloud.capacity} rows")
+            begin_idx, levels, join = ragged_geometry["begin_idx"], ragged_geometry["levels"], (lambda: None)
+        else:
+            counts = self._ragged_counts(cloud)
+            total = sum(counts)
         rows = cloud.packed[:total]                # the tight view: the encoder's dense layers see real rows only
         offsets = cloud.offsets
         coords = rows[:, :3].contiguous() if self.has_features else rows.contiguous()
-        begin_idx, levels, join = ops.geometry_pyramid_ragged(coords, offsets, max(counts), tb.k, npoints, ks)
+        if ragged_geometry is None:
+            begin_idx, levels, join = ops.geometry_pyramid_ragged(coords, offsets, max(counts), tb.k, npoints, ks)
         xyz = coords.view(1, total, 3)
         if self.has_features:
             feats = tb(xyz, ops.linear(rows[:, 3:].unsqueeze(0), self.enc_sdf), idx=begin_idx)
@@ -161,7 +210,7 @@ class PointTransformerEncoder(nn.Module):
         n1 = npoints[0]
         _, down = self.transition_downs[0](xyz, feats, levels[0])              # query side [1,B*n1,.] against [1,total,.]
         entered = (levels[0]["new_xyz"].view(B, n1, 3), down.reshape(B, n1, down.shape[-1]))
-        return self._below_begin(None, None, levels, None, None, entered=entered)
+        return self._below_begin(None, None, levels, ragged_geometry, None, entered=entered)
 
     def _below_begin(self, xyz, feats, levels, geometry, prefetch, entered=None):
         """Everything below transformer_begin.  ``entered``: (centres [B,n1,3], features [B,n1,d]) when the first transition down
@@ -179,10 +228,10 @@ class PointTransformerEncoder(nn.Module):
         # the final blocks all search the same cloud with the same k: one kNN (and one inverse list) for all
         final_idx = geometry.get("final_idx") if geometry is not None else None
         final_inv = geometry.get("final_inv") if geometry is not None else None
+        final_rel = geometry.get("final_rel") if geometry is not None else None      # (cached by ragged_geometry() alone)
         # (... also when they attend to the whole cloud, group_all: one arange index tensor and one list instead of one per block --
         # a list build is a launch on the forward chain, where a kernel's microsecond is a step's microsecond)
         same = len({(blk.group_all, blk.k) for blk in self.final_transformers}) == 1
-        final_rel = None
         for blk, mlp in zip(self.final_transformers, self.final_elementwise):
             if final_idx is None and (same or not blk.group_all):
                 n = xyz.shape[1]

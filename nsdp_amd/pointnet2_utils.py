@@ -567,6 +567,75 @@ def handle_rows(cano, src: torch.Tensor, bounds, params: torch.Tensor, rows: tor
     return rows
 
 
+# The same two entries over packed rows (include/nsdp_handles_ragged.h, csrc/handles_ragged.hip): B meshes of different sizes.
+def _packed3(what, t, cap=None):
+    if not torch.is_tensor(t) or t.dim() != 2 or t.shape[1] != 3 or (cap is not None and t.shape[0] != cap):
+        raise _lib.NsdpHipError(f"{what} must be packed ({'cap' if cap is None else cap}, 3), got "
+                                f"{tuple(t.shape) if torch.is_tensor(t) else type(t).__name__}")
+
+
+def _offsets_batch(what, offsets):
+    if not torch.is_tensor(offsets) or offsets.dim() != 1 or offsets.numel() < 2:
+        raise _lib.NsdpHipError(f"{what}: offsets must be (B+1) int32 with B >= 1, got "
+                                f"{tuple(offsets.shape) if torch.is_tensor(offsets) else type(offsets).__name__}")
+    return int(offsets.numel()) - 1
+
+
+def handle_bounds_ragged(cano: torch.Tensor, offsets: torch.Tensor, n_max: int, workspace=None, out=None) -> torch.Tensor:
+    """``handle_bounds`` of every shape of a packed set (nsdp_handle_bounds_ragged): cano (cap,3) fp32, offsets (B+1) int32 on
+    the device, ``n_max`` an upper bound of the largest shape -> (B,6) fp32, the bits ``handle_bounds`` gives on each shape
+    alone; a shape without rows gets the reductions' identities (two NaN patterns, named in the header).  The host never reads
+    the offsets.  ``workspace``: a buffer of the caller's, else allocated here; ``out``: a (B,6) buffer."""
+    with on_device(cano):
+        _packed3("cano", cano)
+        B, cap, n_max = _offsets_batch("handle_bounds_ragged", offsets), int(cano.shape[0]), int(n_max)
+        fn = lib().nsdp_handle_bounds_ragged_workspace_bytes
+        fn.restype = ctypes.c_size_t
+        need = int(fn(_c_int(B), _c_int(cap), _c_int(n_max)))
+        if need == 0:
+            raise _lib.NsdpHipError(f"handle_bounds_ragged: B={B} shapes in cap={cap} rows with n_max={n_max} outside 1..65535, "
+                                    f"1.., 1..{HANDLE_MAX_POINTS}")
+        if workspace is None:
+            workspace = torch.empty((need // 4,), dtype=torch.int32, device=cano.device)
+        elif not (workspace.is_cuda and workspace.is_contiguous() and workspace.numel() * workspace.element_size() >= need):
+            raise _lib.NsdpHipError(f"handle_bounds_ragged: the workspace must be a contiguous GPU tensor of at least {need} bytes")
+        bounds = torch.empty((B, 6), dtype=torch.float32, device=cano.device) if out is None else out
+        if tuple(bounds.shape) != (B, 6):
+            raise _lib.NsdpHipError(f"handle_bounds_ragged: out must be ({B}, 6), got {tuple(bounds.shape)}")
+        check(lib().nsdp_handle_bounds_ragged(fptr(cano, "cano"), iptr(offsets, "offsets"), _c_int(B), _c_int(cap), _c_int(n_max),
+                                              optptr(workspace), fptr(bounds, "bounds"), stream_ptr()), "nsdp_handle_bounds_ragged")
+    return bounds
+
+
+def handle_rows_ragged(cano, src: torch.Tensor, offsets: torch.Tensor, bounds, params: torch.Tensor, rows: torch.Tensor,
+                       handle_mask=None, move_mask=None, tgt=None, handle_out=None, move_out=None) -> torch.Tensor:
+    """``handle_rows`` over packed rows (nsdp_handle_rows_ragged): src (cap,3), offsets (B+1) int32 on the device, ``params``
+    (B,8) one drag per shape, ``bounds`` (B,6); columns 3..6 of ``rows`` (cap,7) are written for the rows of the B shapes,
+    columns 0..2 and the padding rows never.  ``handle_mask`` / ``move_mask`` (cap,) uint8 or bool, together: they replace the
+    rule (cano and bounds may then be None).  ``tgt`` (cap,3), ``handle_out`` / ``move_out`` (cap,): optional outputs.  Returns
+    ``rows``."""
+    with on_device(src):
+        _packed3("src", src)
+        B, cap = _offsets_batch("handle_rows_ragged", offsets), int(src.shape[0])
+        if cano is not None:
+            _packed3("cano", cano, cap)
+        if tgt is not None:
+            _packed3("tgt", tgt, cap)
+        if not torch.is_tensor(rows) or tuple(rows.shape) != (cap, 7):
+            raise _lib.NsdpHipError(f"handle_rows_ragged: src ({cap},3) goes with rows ({cap},7), got "
+                                    f"{tuple(rows.shape) if torch.is_tensor(rows) else type(rows).__name__}")
+        if tuple(params.shape) != (B, HANDLE_PARAM_WORDS) or (bounds is not None and tuple(bounds.shape) != (B, 6)):
+            raise _lib.NsdpHipError(f"handle_rows_ragged: params must be ({B}, {HANDLE_PARAM_WORDS}) int32 and bounds ({B}, 6)")
+        check(lib().nsdp_handle_rows_ragged(optptr(None) if cano is None else fptr(cano, "cano"), fptr(src, "src"),
+                                            iptr(offsets, "offsets"), optptr(None) if bounds is None else fptr(bounds, "bounds"),
+                                            iptr(params, "params"), _bytes_ptr(handle_mask, "handle_mask", (cap,)),
+                                            _bytes_ptr(move_mask, "move_mask", (cap,)), _c_int(B), _c_int(cap), fptr(rows, "rows"),
+                                            optptr(None) if tgt is None else fptr(tgt, "tgt"),
+                                            _bytes_ptr(handle_out, "handle_out", (cap,)), _bytes_ptr(move_out, "move_out", (cap,)),
+                                            stream_ptr()), "nsdp_handle_rows_ragged")
+    return rows
+
+
 # ------------------------------------------------------------------------------------------------
 # autograd Functions with the reference's names and signatures
 # ------------------------------------------------------------------------------------------------

@@ -1,6 +1,7 @@
 """An editing session's drag against the call it replaces, in one process on one GPU (profiles/edit_session.txt).
 
     python tools/bench_edit.py [--sizes 5000,25000,100000] [--reps 5] [--batch 1]
+    python tools/bench_edit.py --vertex-counts 25000,9000,40000,12000 [--reps 5]      (profiles/edit_session_ragged.txt)
 
 The tosca user-handle configuration's model (FlowArbitrary, npoints_per_layer [5000, 500, 100]; procedural weights), the cloud
 = the vertex set (the reference's user-handle data set), one mesh of N uniform vertices per size.  Per size one JSON line with the
@@ -19,6 +20,16 @@ variant; every drag of a window has another translation:
     equal             the session's predictions, eager and replayed, are bit-equal to the full call's.
 
 The ratios ``full_eager / drag_eager`` and ``full_graph / drag_graph`` are reported as they come out; nothing is tuned to them.
+
+``--vertex-counts``: B meshes of these vertex counts, packed, the cloud = the vertex set, through a RaggedEditSession -- against
+the two ways a packed batch could be dragged without it, interleaved in the same way:
+
+    drag_eager_ms / drag_graph_ms         RaggedEditSession.drag, op by op / copy + replay;
+    full_eager_ms                         test_on_batch_with_arbitrary on the ragged data_dict of the same drag (a step with a ragged
+                                          cloud reads the counts on the host and is not captured: there is no full_graph);
+    per_mesh_eager_ms / per_mesh_graph_ms B batch-1 EditSessions, one per mesh, dragged in turn;
+    open_ms                               RaggedEditSession.reopen();
+    bounds_ms, rows_ms                    nsdp_handle_bounds_ragged and nsdp_handle_rows_ragged alone (windows of 200 launches).
 """
 import argparse
 import json
@@ -32,10 +43,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from nsdp_amd import pointnet2_utils as pu, synth                                  # noqa: E402
 from nsdp_amd.config import default_config                                         # noqa: E402
-from nsdp_amd.edit import EditSession, HandleSpec, pack_params, reference_data_dict  # noqa: E402
+from nsdp_amd.edit import EditSession, HandleSpec, RaggedEditSession, pack_params, reference_data_dict  # noqa: E402
 from nsdp_amd.model import build_model                                             # noqa: E402
 from nsdp_amd.model.flow_arbitrary import test_on_batch_with_arbitrary             # noqa: E402
 from nsdp_amd.query_shard import QueryShards, query_sharded                        # noqa: E402
+from nsdp_amd.ragged import RaggedPoints                                           # noqa: E402
 
 SPEC = HandleSpec("head", (-0.15, -0.2, -0.2), 0.1, False)      # config/tosca/head.yaml's drag
 KEYS = ("verts_tgt_pred", "surface_samples_tgt_pred")
@@ -120,9 +132,81 @@ def bench_size(model, N, batch, reps, dev):
     return line
 
 
+def bench_ragged(model, counts, reps, dev):
+    B = len(counts)
+    meshes = [torch.from_numpy(synth.uniform(1000 + b, "mesh_verts", (1, n, 3), -0.5, 0.5)).to(dev) for b, n in enumerate(counts)]
+    verts = RaggedPoints.from_list([m[0] for m in meshes])
+    calls = 20 if sum(counts) <= 25000 else 10
+
+    def translation(i):
+        return tuple(v * (1.0 + 0.01 * (i % 7)) for v in SPEC.translation)
+
+    eager, graphed = RaggedEditSession(model, verts), RaggedEditSession(model, verts, graph=True)
+    singles = [EditSession(model, m) for m in meshes]
+    singles_graph = [EditSession(model, m, graph=True) for m in meshes]
+    # the ragged data_dicts of the drags of a window, ahead of it: the session's own reference-shaped inputs (bit-equal to the
+    # torch-built ones, tests/test_edit_session_ragged_gpu.py)
+    dicts = []
+    for i in range(7):
+        inputs = eager.drag(SPEC.part, translation(i), with_inputs=True)["surface_samples_inputs"]
+        dicts.append({"surface_samples_inputs": inputs, "surface_samples_src": inputs.columns(0, 3), "verts_src": verts})
+    variants = {
+        "drag_eager_ms": lambda i: eager.drag(SPEC.part, translation(i), clone=False),
+        "drag_graph_ms": lambda i: graphed.drag(SPEC.part, translation(i), clone=False),
+        "full_eager_ms": lambda i: test_on_batch_with_arbitrary(model, dict(dicts[i % 7]), None),
+        "per_mesh_eager_ms": lambda i: [s.drag(SPEC.part, translation(i), clone=False) for s in singles],
+        "per_mesh_graph_ms": lambda i: [s.drag(SPEC.part, translation(i), clone=False) for s in singles_graph],
+    }
+    want = test_on_batch_with_arbitrary(model, dict(dicts[3]), None)[1]
+    got = [eager.drag(SPEC.part, translation(3)), graphed.drag(SPEC.part, translation(3))]
+    equal = all(torch.equal(g[k].packed, want[k].packed) for g in got for k in KEYS)
+    for fn in variants.values():      # warm-up of every variant (the first replayed drags capture)
+        for i in range(3):
+            fn(i)
+    times = {k: [] for k in variants}
+    times["open_ms"] = []
+    for _ in range(reps):
+        for k, fn in variants.items():
+            times[k].append(window(fn, calls))
+        times["open_ms"].append(window(lambda i: eager.reopen(), 1))
+    # the two kernels alone
+    cap, n_max = verts.capacity, max(counts)
+    params = torch.from_numpy(pack_params(B, SPEC.part, SPEC.translation, SPEC.partial_range, SPEC.cliptail)).to(dev)
+    rows, tgt = torch.empty(cap, 7, device=dev), torch.empty(cap, 3, device=dev)
+    flags = torch.empty(cap, dtype=torch.uint8, device=dev)
+    bounds = pu.handle_bounds_ragged(verts.packed, verts.offsets, n_max)
+    ws = torch.empty(1 << 16, dtype=torch.int32, device=dev)
+    kernels = {"bounds_ms": lambda i: pu.handle_bounds_ragged(verts.packed, verts.offsets, n_max, workspace=ws, out=bounds),
+               "rows_ms": lambda i: pu.handle_rows_ragged(verts.packed, verts.packed, verts.offsets, bounds, params, rows, tgt=tgt,
+                                                          handle_out=flags)}
+    for fn in kernels.values():
+        fn(0)
+    for k in kernels:
+        times[k] = []
+    for _ in range(reps):
+        for k, fn in kernels.items():
+            times[k].append(window(fn, KERNEL_WINDOW))
+    pu.check_fps_cluster()
+    line = {"vertex_counts": list(counts), "batch": B, "calls_per_window": calls, "reps": reps,
+            "handle_points": int(eager.drag(SPEC.part, SPEC.translation)["cano_handle_sample_idx"].packed.sum()),
+            **{k: stats(v) for k, v in times.items()}, "equal": bool(equal),
+            "graph_nodes": {"session": graphed._steps[(False, False)].info}, "replays": graphed.replays}
+    med = {k: statistics.median(v) for k, v in times.items()}
+    line["full_eager_over_drag_eager"] = round(med["full_eager_ms"] / med["drag_eager_ms"], 3)
+    line["full_eager_over_drag_graph"] = round(med["full_eager_ms"] / med["drag_graph_ms"], 3)
+    line["per_mesh_eager_over_drag_eager"] = round(med["per_mesh_eager_ms"] / med["drag_eager_ms"], 3)
+    line["per_mesh_graph_over_drag_graph"] = round(med["per_mesh_graph_ms"] / med["drag_graph_ms"], 3)
+    for s in [eager, graphed] + singles + singles_graph:
+        s.close()
+    return line
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--sizes", default="5000,25000,100000")
+    ap.add_argument("--vertex-counts", action="append", default=None, metavar="n1,n2,...",
+                    help="a packed batch of meshes of these vertex counts through a RaggedEditSession (may be given several times; "
+                         "replaces --sizes and --batch)")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--batch", type=int, default=1)
     args = ap.parse_args(argv)
@@ -136,6 +220,11 @@ def main(argv=None):
     model.load_state_dict({k: torch.from_numpy(v) for k, v in state.items()})
     model.to(dev).eval()
     print(json.dumps({"tool": "bench_edit", "device": torch.cuda.get_device_name(0), "model": config["model"]}), flush=True)
+    if args.vertex_counts:
+        with torch.no_grad():
+            for text in args.vertex_counts:
+                print(json.dumps(bench_ragged(model, tuple(int(v) for v in text.split(",")), args.reps, dev)), flush=True)
+        return 0
     lines = []
     with torch.no_grad():
         for N in (int(s) for s in args.sizes.split(",")):
