@@ -2,112 +2,32 @@
 // handle rule (dataset/utils.py: cano_handle_user_define), the dragged target and columns 3..6 of the deformation network's
 // input rows -- with the drag parameters read from device memory, so that a captured graph serves every drag.
 //
-//   bounds   partial: grid (G, B), G = ceil(n / kPointsPerGroup) capped at kMaxGroups.  A workgroup strides over its shape's
-//            points, keeps six running extremes per lane as order-preserving integer keys of the fp32 bits, reduces them over
-//            the wave by shuffles and over its four waves through LDS, and writes its six keys to the workspace.  G <= ceil(n /
-//            kThreads), so every workgroup owns at least one point and every workspace word is written.
-//            final: one wave per shape reduces the G partials and stores the six floats.
-//            Integer min / max on the keys is a total order: the result is the same for every split of the points.
-//   rows     one lane per point, grid (ceil(n / kThreads), B).  The shape's parameters and bounds are uniform loads; the point's
-//            rows are 12-byte loads and the stores are per-dword vector stores (a [n, 7] row is 28 bytes: columns 3..6 of it are
-//            never 16-byte aligned for every row).
+// This file is the RECTANGULAR layout: B shapes of n points each, row p = b * n + i.  What a workgroup does with its shape's
+// points and what a lane does with its row -- the keys and their reductions, the final-bounds kernel, the rule, the target and
+// the stores -- is handles_rule.h, shared with handles_ragged.hip; here are the two kernels that name the rows, the argument
+// checks and the launches.
 //
-// This file is built with -ffp-contract=off and the arithmetic is spelled with the __f*_rn intrinsics: one rounding per
-// operation, no fused multiply-add, and the products by 0.0f / 1.0f are real multiplications (0 * NaN = NaN, -0.15f * 0 = -0).
-#include "common.h"
-
-#include "../../include/nsdp_handles.h"
+//   bounds   partial: grid (G, B), G = ceil(n / kPointsPerGroup); workgroup (g, b) reduces its share of shape b to six keys in
+//            the workspace.  G <= ceil(n / kThreads), so every workgroup owns at least one point.
+//            final: one wave per shape reduces the G partials and stores the six floats.
+//   rows     one lane per point, grid (ceil(n / kThreads), B).
+//
+// Built with -ffp-contract=off, as handles_rule.h requires: one rounding per operation, no fused multiply-add.
+#include "handles_rule.h"
 
 namespace {
 
-constexpr int kMaxPoints = 1 << 20;
-constexpr int kThreads = 256;
-constexpr int kPointsPerGroup = 4096;      // sixteen points per lane
 constexpr int kMaxGroups = 256;            // n = 2^20 at kPointsPerGroup
 static_assert(kMaxPoints / kPointsPerGroup == kMaxGroups, "the largest cloud takes the largest grid");
 
 inline bool refused(int B, int n) { return B < 1 || B > 65535 || n < 1 || n > kMaxPoints; }
 
-inline int groups_of(int n) {
-  const int g = nsdp::ceil_div(n, kPointsPerGroup);
-  return g < kMaxGroups ? g : kMaxGroups;
-}
-
-// fp32 bits -> unsigned key with key(a) < key(b) exactly when a sorts before b (negative values mirrored, -0 below +0)
-__device__ __forceinline__ uint32_t key_of(float v) {
-  const uint32_t u = __float_as_uint(v);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-__device__ __forceinline__ float value_of(uint32_t key) {
-  return __uint_as_float((key & 0x80000000u) ? (key & 0x7fffffffu) : ~key);
-}
-
-__device__ __forceinline__ void wave_extremes(uint32_t (&lo)[3], uint32_t (&hi)[3]) {
-#pragma unroll
-  for (int off = 32; off; off >>= 1) {
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      lo[c] = min(lo[c], static_cast<uint32_t>(__shfl_xor(static_cast<int>(lo[c]), off)));
-      hi[c] = max(hi[c], static_cast<uint32_t>(__shfl_xor(static_cast<int>(hi[c]), off)));
-    }
-  }
-}
+inline int groups_of(int n) { return nsdp::ceil_div(n, kPointsPerGroup); }
 
 __global__ __launch_bounds__(kThreads) void handle_bounds_partial_kernel(const float *__restrict__ cano_all, int n, int G,
                                                                          uint32_t *__restrict__ part_all) {
-  __shared__ uint32_t red[kThreads / 64][6];
   const int b = blockIdx.y, g = blockIdx.x;
-  const float *cano = cano_all + static_cast<long long>(b) * n * 3;
-  uint32_t lo[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, hi[3] = {0u, 0u, 0u};
-  for (long long i = static_cast<long long>(g) * kThreads + threadIdx.x; i < n; i += static_cast<long long>(G) * kThreads) {
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const uint32_t k = key_of(cano[i * 3 + c]);
-      lo[c] = min(lo[c], k);
-      hi[c] = max(hi[c], k);
-    }
-  }
-  wave_extremes(lo, hi);
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      red[wave][c] = lo[c];
-      red[wave][3 + c] = hi[c];
-    }
-  }
-  __syncthreads();
-  if (threadIdx.x < 6) {
-    const int c = threadIdx.x;
-    uint32_t v = red[0][c];
-#pragma unroll
-    for (int w = 1; w < kThreads / 64; ++w) v = c < 3 ? min(v, red[w][c]) : max(v, red[w][c]);
-    part_all[(static_cast<long long>(b) * G + g) * 6 + c] = v;
-  }
-}
-
-__global__ __launch_bounds__(64) void handle_bounds_final_kernel(const uint32_t *__restrict__ part_all, int G,
-                                                                 float *__restrict__ bounds_all) {
-  const int b = blockIdx.x;
-  const uint32_t *part = part_all + static_cast<long long>(b) * G * 6;
-  uint32_t lo[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, hi[3] = {0u, 0u, 0u};
-  for (int g = threadIdx.x; g < G; g += 64) {
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      lo[c] = min(lo[c], part[g * 6 + c]);
-      hi[c] = max(hi[c], part[g * 6 + 3 + c]);
-    }
-  }
-  wave_extremes(lo, hi);
-  if (threadIdx.x == 0) {
-    float *bounds = bounds_all + static_cast<long long>(b) * 6;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      bounds[c] = value_of(lo[c]);
-      bounds[3 + c] = value_of(hi[c]);
-    }
-  }
+  bounds_partial(cano_all + static_cast<long long>(b) * n * 3, n, g, G, part_all + (static_cast<long long>(b) * G + g) * 6);
 }
 
 template <bool MASKS>
@@ -122,55 +42,8 @@ __global__ __launch_bounds__(kThreads) void handle_rows_kernel(const float *__re
   const long long il = static_cast<long long>(blockIdx.x) * kThreads + threadIdx.x;
   if (il >= n) return;
   const long long p = static_cast<long long>(b) * n + il;      // the point's row in every (B, n, .) operand
-  const uint32_t *prm = params_all + static_cast<long long>(b) * NSDP_HANDLE_PARAM_WORDS;
-  const float dx = __uint_as_float(prm[NSDP_HANDLE_DX]), dy = __uint_as_float(prm[NSDP_HANDLE_DY]),
-              dz = __uint_as_float(prm[NSDP_HANDLE_DZ]);
-  bool handle, move;
-  if (MASKS) {
-    handle = handle_mask[p] != 0;
-    move = move_mask[p] != 0;
-  } else {
-    const int part = static_cast<int>(prm[NSDP_HANDLE_PART]);
-    const bool clip = prm[NSDP_HANDLE_CLIPTAIL] != 0;
-    const float r = __uint_as_float(prm[NSDP_HANDLE_RANGE]);
-    const float *bounds = bounds_all + static_cast<long long>(b) * 6;
-    const float lo_y = bounds[1], lo_z = bounds[2], hi_y = bounds[4];
-    const float x = cano_all[p * 3], y = cano_all[p * 3 + 1], z = cano_all[p * 3 + 2];
-    const bool head = y < __fadd_rn(lo_y, r);
-    bool tail = y > __fsub_rn(hi_y, r);
-    if (clip) tail = tail && z > -r;
-    const bool foot = z < __fadd_rn(lo_z, r);
-    handle = head || tail || foot;
-    const bool left = foot && x > 0.0f, right = foot && x < 0.0f, front = foot && y < 0.0f, behind = foot && y > 0.0f;
-    switch (part) {
-      case NSDP_HANDLE_HEAD: move = head; break;
-      case NSDP_HANDLE_TAIL: move = tail; break;
-      case NSDP_HANDLE_FRONTLEFTFOOT: move = left && front; break;
-      case NSDP_HANDLE_FRONTRIGHTFOOT: move = right && front; break;
-      case NSDP_HANDLE_BEHINDLEFTFOOT: move = left && behind; break;
-      case NSDP_HANDLE_BEHINDRIGHTFOOT: move = right && behind; break;
-      default: move = false; break;
-    }
-  }
-  const float m = move ? 1.0f : 0.0f, h = handle ? 1.0f : 0.0f;
-  const float tx = __fadd_rn(src_all[p * 3], __fmul_rn(dx, m));
-  const float ty = __fadd_rn(src_all[p * 3 + 1], __fmul_rn(dy, m));
-  const float tz = __fadd_rn(src_all[p * 3 + 2], __fmul_rn(dz, m));
-  float *row = rows_all + p * 7;
-  row[3] = __fmul_rn(tx, h);
-  row[4] = __fmul_rn(ty, h);
-  row[5] = __fmul_rn(tz, h);
-  row[6] = h;
-  if (tgt_all) {
-    tgt_all[p * 3] = tx;
-    tgt_all[p * 3 + 1] = ty;
-    tgt_all[p * 3 + 2] = tz;
-  }
-  if (handle_out) handle_out[p] = handle ? 1 : 0;
-  if (move_out) move_out[p] = move ? 1 : 0;
+  handle_row<MASKS>(p, b, cano_all, src_all, bounds_all, params_all, handle_mask, move_mask, rows_all, tgt_all, handle_out, move_out);
 }
-
-inline bool misaligned4(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3) != 0; }
 
 }  // namespace
 

@@ -109,13 +109,12 @@ def pack_params(B, part, translation, partial_range, cliptail):
     return words
 
 
-def refusal(model, verts_src, surface=None, cano=None, surface_cano=None):
-    """Why a session cannot be opened on these arguments (None: it can), each reason named."""
+def _networks_or_refusal(model):
+    """The reasons that depend on the model alone -- its type, training mode, autograd -- as a string; without one, the list of
+    the model's networks, the deformation network last."""
     import torch
-    from . import precision
     from .model.deformation_networks import Deformation_Networks
     from .model.flow_arbitrary import FlowArbitrary
-    from .ragged import RaggedPoints
     if isinstance(model, FlowArbitrary):
         nets = [model.model_canonicalize, model.model_deform]
     elif isinstance(model, Deformation_Networks):
@@ -128,19 +127,38 @@ def refusal(model, verts_src, surface=None, cano=None, surface_cano=None):
     if torch.is_grad_enabled():
         return ("autograd is enabled: a session runs the inference kernels over cached tensors and records no graph -- open it "
                 "and drag under torch.no_grad()")
+    return nets
+
+
+def _network_refusal(net2, encoder_needs):
+    """The reasons that depend on the storage type and the deformation network; ``encoder_needs``: the methods of its encoder
+    the session's layout calls."""
+    from . import precision
+    if precision.is_bf16():
+        return "bf16 storage (NSDP_STORAGE=bf16): the session is built and tested in fp32 storage only"
+    if net2.no_input_corr:
+        return "this network does not read the handle columns (no_input_corr: a backward-type network): a drag would change nothing"
+    if not (all(hasattr(net2.encoder, m) for m in encoder_needs) and hasattr(net2.decoder, "geometry")):
+        return (f"the {type(net2.encoder).__name__} / {type(net2.decoder).__name__} pair has no geometry(): it searches inside "
+                "its forward pass only, so its index sets cannot be cached across drags")
+    return None
+
+
+def refusal(model, verts_src, surface=None, cano=None, surface_cano=None):
+    """Why a session cannot be opened on these arguments (None: it can), each reason named."""
+    import torch
+    from .ragged import RaggedPoints
+    nets = _networks_or_refusal(model)
+    if isinstance(nets, str):
+        return nets
     given = {"verts_src": verts_src, "surface": surface, "cano": cano, "surface_cano": surface_cano}
     for name, t in given.items():
         if isinstance(t, RaggedPoints):
             return (f"ragged inputs: {name} is a RaggedPoints -- an EditSession holds one rectangular [B, n, 3] set per role; "
                     "RaggedEditSession takes a packed batch of meshes of different sizes")
-    if precision.is_bf16():
-        return "bf16 storage (NSDP_STORAGE=bf16): the session is built and tested in fp32 storage only"
-    net2 = nets[-1]
-    if net2.no_input_corr:
-        return "this network does not read the handle columns (no_input_corr: a backward-type network): a drag would change nothing"
-    if not (hasattr(net2.encoder, "geometry") and hasattr(net2.decoder, "geometry")):
-        return (f"the {type(net2.encoder).__name__} / {type(net2.decoder).__name__} pair has no geometry(): it searches inside "
-                "its forward pass only, so its index sets cannot be cached across drags")
+    why = _network_refusal(nets[-1], ("geometry",))
+    if why is not None:
+        return why
     for name, t in given.items():
         if t is None:
             continue
@@ -160,7 +178,149 @@ def refusal(model, verts_src, surface=None, cano=None, surface_cano=None):
     return None
 
 
-class EditSession:
+class _Session:
+    """What an editing session is in either layout: the checks at open, the bookkeeping, one drag up to its dispatch -- the
+    parameter copy, the mask buffers, capture or eager by (masks, vert_masks) -- and the end.  A layout (EditSession: rectangular
+    sets; RaggedEditSession: packed ones) gives
+
+      _refusal(model, verts_src, surface, cano, surface_cano)   why a session cannot be opened on these (None: it can);
+      _hold(verts_src, surface, cano, surface_cano)             keeps the sets as it wants them, contiguous;
+      _open()                                                   computes everything cached per source and weights;
+      _layout()                                                 (B, the tensor that names the device, the shape of a mask over
+                                                                the cloud, of one over the vertices);
+      _enqueue(masks, vert_masks)                               the GPU work of a drag behind the copies;
+      _result(pred, own, own_pred, have_verts, with_inputs)     the dict a drag returns;
+      _cached                                                   the attributes close() lets go of."""
+
+    def __init__(self, model, verts_src, surface=None, cano=None, surface_cano=None, partial_range=0.1, cliptail=False,
+                 graph=False, max_streams=None):
+        why = self._refusal(model, verts_src, surface, cano, surface_cano)
+        if why is not None:
+            raise ValueError(self._refused + why)
+        from . import query_shard
+        from .model.flow_arbitrary import FlowArbitrary
+        self.model = model
+        self.flow = isinstance(model, FlowArbitrary)
+        self.net = model.model_deform if self.flow else model
+        # one decode standing for two, and network 1 decoding one set where the step function decodes the concatenation: both
+        # rest on the decoder treating every query row on its own -- the fused fp32 decoder (query_shard names what is not)
+        for net in ([model.model_canonicalize, self.net] if self.flow else [self.net]):
+            query_shard.require_supported(net)
+        self._hold(verts_src, surface, cano, surface_cano)
+        self.partial_range, self.cliptail = float(partial_range), bool(cliptail)
+        self.graph, self.max_streams = bool(graph), max_streams
+        self.replays = self.eager_calls = 0
+        self._steps = {}
+        self._open()
+
+    @property
+    def _refused(self):
+        return type(self).__name__ + " refused: "
+
+    def reopen(self):
+        """Recompute everything the session caches (after the weights changed) and drop the captured graphs."""
+        why = self._refusal(self.model, self.verts, None if self.same else self.surface)
+        if why is not None:
+            raise ValueError(self._refused + why)
+        self._drop_graphs()
+        self._open()
+        return self
+
+    # ------------------------------------------------------------------ one drag
+    def _mask_buffer(self, name, like_rows, value, device):
+        import torch
+        buf = getattr(self, name)
+        if buf is None:
+            buf = torch.empty(like_rows, dtype=torch.uint8, device=device)
+            setattr(self, name, buf)
+        if not torch.is_tensor(value) or not value.is_cuda:
+            raise ValueError(self._refused + "CPU tensors: the masks of a drag must be GPU tensors")
+        if value.dtype not in (torch.bool, torch.uint8) or tuple(value.shape) != tuple(like_rows):
+            raise ValueError(f"drag: a mask must be bool / uint8 {tuple(like_rows)}, got {value.dtype} {tuple(value.shape)}")
+        buf.copy_(value, non_blocking=True)
+
+    def drag(self, part=None, translation=(0.0, 0.0, 0.0), handle_mask=None, move_mask=None, vert_handle_mask=None,
+             vert_move_mask=None, partial_range=None, cliptail=None, with_inputs=False, clone=True):
+        """One drag of every shape.  By rule: ``part`` (a name of PARTS, one per shape, or a HandleSpec) moves by ``translation``
+        ((dx, dy, dz) or [B, 3]).  By explicit regions: ``handle_mask`` / ``move_mask`` over the cloud (bool / uint8 on the GPU:
+        [B, n] for a rectangular cloud, (scap,) for a packed one) replace the rule; with a separate cloud ``vert_handle_mask`` /
+        ``vert_move_mask`` ([B, V], packed (cap,)) do so for the vertices (without them ``verts_tgt`` and
+        ``cano_handle_vert_idx`` are None).
+
+        Returns ``verts_tgt_pred``, ``surface_samples_tgt_pred``, ``verts_tgt``, ``cano_handle_vert_idx`` and
+        ``cano_handle_sample_idx``, and with ``with_inputs`` ``surface_samples_inputs`` = [src | mask * tgt | mask], what the step
+        function takes as it is -- shaped as the session's ``_result`` says.  The tensors are the caller's own; ``clone=False``
+        hands out the session's buffers, overwritten by the next drag."""
+        import torch
+        from ._lib import on_device
+        if torch.is_grad_enabled():
+            raise ValueError(self._refused + "autograd is enabled -- drag under torch.no_grad()")
+        if self.model.training:
+            raise ValueError(self._refused + "the model is in training mode -- call model.eval() (and reopen() if the weights "
+                             "changed)")
+        if isinstance(part, HandleSpec):
+            spec, part, translation = part, part.part, part.translation
+            partial_range = spec.partial_range if partial_range is None else partial_range
+            cliptail = spec.cliptail if cliptail is None else cliptail
+        masks = handle_mask is not None or move_mask is not None
+        B, on, cloud_rows, vert_rows = self._layout()
+        if masks:
+            if handle_mask is None or move_mask is None or part is not None:
+                raise ValueError("drag: handle_mask and move_mask go together and replace `part`")
+            if (vert_handle_mask is None) != (vert_move_mask is None) or (self.same and vert_handle_mask is not None):
+                raise ValueError("drag: vert_handle_mask and vert_move_mask go together, with a separate cloud only")
+            part = 0
+        elif part is None:
+            raise ValueError(f"drag: name the part that moves (one of {PARTS}) or give handle_mask and move_mask")
+        elif vert_handle_mask is not None or vert_move_mask is not None:
+            raise ValueError("drag: vertex masks go with handle_mask and move_mask")
+        vert_masks = masks and vert_handle_mask is not None
+        words = pack_params(B, part, translation, self.partial_range if partial_range is None else partial_range,
+                            self.cliptail if cliptail is None else cliptail)
+        with on_device(on):
+            # the one host-to-device copy of a drag, stream-ordered in front of the kernels that read it (pageable memory: the
+            # runtime has taken the bytes when copy_ returns, so the host array is free at once)
+            self.params.copy_(torch.from_numpy(words), non_blocking=True)
+            if masks:
+                self._mask_buffer("_mask_h", cloud_rows, handle_mask, on.device)
+                self._mask_buffer("_mask_m", cloud_rows, move_mask, on.device)
+                if vert_masks:
+                    self._mask_buffer("_vmask_h", vert_rows, vert_handle_mask, on.device)
+                    self._mask_buffer("_vmask_m", vert_rows, vert_move_mask, on.device)
+            key = (masks, vert_masks)
+            if self.graph:
+                if key not in self._steps:
+                    from .graph_step import GraphedStep
+                    self._steps[key] = GraphedStep(lambda: self._enqueue(*key), self.max_streams,
+                                                   weights_change=False).capture(warmup=1)
+                self.replays += 1
+                pred = self._steps[key]()
+            else:
+                self.eager_calls += 1
+                pred = self._enqueue(*key)
+            own = (lambda t: t.clone()) if clone else (lambda t: t)      # the session's buffers: the next drag overwrites them
+            own_pred = own if self.graph else (lambda t: t)              # (an eager drag's predictions are fresh tensors)
+            return self._result(pred, own, own_pred, self.same or not masks or vert_masks, with_inputs)
+
+    # ------------------------------------------------------------------ the end
+    def _drop_graphs(self):
+        for step in self._steps.values():
+            step.close()
+        self._steps = {}
+
+    def close(self):
+        self._drop_graphs()
+        for name in self._cached:
+            setattr(self, name, None)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+class EditSession(_Session):
     """See the module text.  ``verts_src`` [B, V, 3] fp32 on the GPU; ``surface`` [B, S, 3]: the cloud network 2 encodes (None:
     the vertex set itself, as in the reference's user-handle data set); ``cano`` / ``surface_cano``: the coordinates the
     bounding-box rule is evaluated on (None: the source coordinates -- what the reference does, every frame of its pairs being
@@ -172,30 +332,18 @@ class EditSession:
     ``graph=True``: the first drag captures everything behind the parameter copy; later drags are copy + replay (``replays``;
     ``eager_calls`` counts drags run op by op)."""
 
-    def __init__(self, model, verts_src, surface=None, cano=None, surface_cano=None, partial_range=0.1, cliptail=False,
-                 graph=False, max_streams=None):
-        why = refusal(model, verts_src, surface, cano, surface_cano)
-        if why is not None:
-            raise ValueError("EditSession refused: " + why)
-        from . import query_shard
-        from .model.flow_arbitrary import FlowArbitrary
-        self.model = model
-        self.flow = isinstance(model, FlowArbitrary)
-        self.net = model.model_deform if self.flow else model
-        # one decode standing for two, and network 1 decoding one set where the step function decodes the concatenation: both
-        # rest on the decoder treating every query row on its own -- the fused fp32 decoder (query_shard names what is not)
-        for net in ([model.model_canonicalize, self.net] if self.flow else [self.net]):
-            query_shard.require_supported(net)
+    _refusal = staticmethod(refusal)
+    _cached = ("geometry", "buf", "_surf_idx")
+
+    def _hold(self, verts_src, surface, cano, surface_cano):
         self.verts = verts_src.contiguous()
         self.same = surface is None
         self.surface = self.verts if self.same else surface.contiguous()
         self.verts_rule = self.verts if cano is None else cano.contiguous()
         self.surface_rule = (self.verts_rule if self.same else self.surface) if surface_cano is None else surface_cano.contiguous()
-        self.partial_range, self.cliptail = float(partial_range), bool(cliptail)
-        self.graph, self.max_streams = bool(graph), max_streams
-        self.replays = self.eager_calls = 0
-        self._steps = {}
-        self._open()
+
+    def _layout(self):
+        return self.verts.shape[0], self.verts, tuple(self.surface.shape[:2]), tuple(self.verts.shape[:2])
 
     # ------------------------------------------------------------------ the cached state
     def _open(self):
@@ -228,15 +376,6 @@ class EditSession:
                 self.verts_handle = torch.empty((B, V), dtype=torch.uint8, device=dev)
                 self._vrows = torch.empty((B, V, 7), dtype=torch.float32, device=dev)      # (the kernel's required output)
 
-    def reopen(self):
-        """Recompute everything the session caches (after the weights changed) and drop the captured graphs."""
-        why = refusal(self.model, self.verts, None if self.same else self.surface)
-        if why is not None:
-            raise ValueError("EditSession refused: " + why)
-        self._drop_graphs()
-        self._open()
-        return self
-
     # ------------------------------------------------------------------ one drag
     def _enqueue(self, masks, vert_masks):
         """Everything of a drag that runs on the GPU behind the parameter copy: capturable, reads device tensors only."""
@@ -257,128 +396,32 @@ class EditSession:
             out["surface_samples_tgt_pred"] = net.decode(self.surf2cano, enc_s)
         return out
 
-    def _mask_buffer(self, name, like_rows, value):
+    def _result(self, pred, own, own_pred, have_verts, with_inputs):
+        """``verts_tgt_pred`` [B, V, 3], ``surface_samples_tgt_pred`` [B, S, 3], ``verts_tgt``, ``cano_handle_vert_idx`` and
+        ``cano_handle_sample_idx`` (bool), and with ``with_inputs`` the reference-shaped ``surface_samples_inputs`` [B, S, 7]
+        = [src | mask * tgt | mask] (what test_on_batch_with_arbitrary and eval_metric take)."""
         import torch
-        buf = getattr(self, name)
-        if buf is None:
-            buf = torch.empty(like_rows, dtype=torch.uint8, device=self.verts.device)
-            setattr(self, name, buf)
-        if not torch.is_tensor(value) or not value.is_cuda:
-            raise ValueError("EditSession refused: CPU tensors: the masks of a drag must be GPU tensors")
-        if value.dtype not in (torch.bool, torch.uint8) or tuple(value.shape) != tuple(like_rows):
-            raise ValueError(f"drag: a mask must be bool / uint8 {tuple(like_rows)}, got {value.dtype} {tuple(value.shape)}")
-        buf.copy_(value, non_blocking=True)
-
-    def drag(self, part=None, translation=(0.0, 0.0, 0.0), handle_mask=None, move_mask=None, vert_handle_mask=None,
-             vert_move_mask=None, partial_range=None, cliptail=None, with_inputs=False, clone=True):
-        """One drag.  By rule: ``part`` (a name of PARTS, or one per shape) moves by ``translation`` ((dx, dy, dz) or [B, 3]).
-        By explicit regions: ``handle_mask`` / ``move_mask`` (bool / uint8 [B, n] over the cloud, on the GPU) replace the rule;
-        with a separate cloud ``vert_handle_mask`` / ``vert_move_mask`` [B, V] do so for the vertices (without them
-        ``verts_tgt`` and ``cano_handle_vert_idx`` are None).  ``part`` may also be a HandleSpec.
-
-        Returns ``verts_tgt_pred`` [B, V, 3], ``surface_samples_tgt_pred`` [B, S, 3], ``verts_tgt``, ``cano_handle_vert_idx``
-        and ``cano_handle_sample_idx`` (bool), and with ``with_inputs`` the reference-shaped ``surface_samples_inputs`` [B, S, 7]
-        = [src | mask * tgt | mask] (what test_on_batch_with_arbitrary and eval_metric take).  The tensors are the caller's own;
-        ``clone=False`` hands out the session's buffers, overwritten by the next drag."""
-        import torch
-        from ._lib import on_device
-        if torch.is_grad_enabled():
-            raise ValueError("EditSession refused: autograd is enabled -- drag under torch.no_grad()")
-        if self.model.training:
-            raise ValueError("EditSession refused: the model is in training mode -- call model.eval() (and reopen() if the "
-                             "weights changed)")
-        if isinstance(part, HandleSpec):
-            spec, part, translation = part, part.part, part.translation
-            partial_range = spec.partial_range if partial_range is None else partial_range
-            cliptail = spec.cliptail if cliptail is None else cliptail
-        masks = handle_mask is not None or move_mask is not None
-        B = self.verts.shape[0]
-        if masks:
-            if handle_mask is None or move_mask is None or part is not None:
-                raise ValueError("drag: handle_mask and move_mask go together and replace `part`")
-            if (vert_handle_mask is None) != (vert_move_mask is None) or (self.same and vert_handle_mask is not None):
-                raise ValueError("drag: vert_handle_mask and vert_move_mask go together, with a separate cloud only")
-            part = 0
-        elif part is None:
-            raise ValueError(f"drag: name the part that moves (one of {PARTS}) or give handle_mask and move_mask")
-        elif vert_handle_mask is not None or vert_move_mask is not None:
-            raise ValueError("drag: vertex masks go with handle_mask and move_mask")
-        vert_masks = masks and vert_handle_mask is not None
-        words = pack_params(B, part, translation, self.partial_range if partial_range is None else partial_range,
-                            self.cliptail if cliptail is None else cliptail)
-        with on_device(self.verts):
-            # the one host-to-device copy of a drag, stream-ordered in front of the kernels that read it (pageable memory: the
-            # runtime has taken the bytes when copy_ returns, so the host array is free at once)
-            self.params.copy_(torch.from_numpy(words), non_blocking=True)
-            if masks:
-                S, V = self.surface.shape[1], self.verts.shape[1]
-                self._mask_buffer("_mask_h", (B, S), handle_mask)
-                self._mask_buffer("_mask_m", (B, S), move_mask)
-                if vert_masks:
-                    self._mask_buffer("_vmask_h", (B, V), vert_handle_mask)
-                    self._mask_buffer("_vmask_m", (B, V), vert_move_mask)
-            key = (masks, vert_masks)
-            if self.graph:
-                if key not in self._steps:
-                    from .graph_step import GraphedStep
-                    self._steps[key] = GraphedStep(lambda: self._enqueue(*key), self.max_streams,
-                                                   weights_change=False).capture(warmup=1)
-                self.replays += 1
-                pred = self._steps[key]()
-            else:
-                self.eager_calls += 1
-                pred = self._enqueue(*key)
-            own = (lambda t: t.clone()) if clone else (lambda t: t)      # the session's buffers: the next drag overwrites them
-            own_pred = own if self.graph else (lambda t: t)              # (an eager drag's predictions are fresh tensors)
-            out = {"verts_tgt_pred": own_pred(pred["verts_tgt_pred"])}
-            out["surface_samples_tgt_pred"] = (out["verts_tgt_pred"] if self.same
-                                               else own_pred(pred["surface_samples_tgt_pred"]))
-            have_verts = self.same or not masks or vert_masks
-            out["verts_tgt"] = own(self.verts_tgt) if have_verts else None
-            out["cano_handle_vert_idx"] = own(self.verts_handle).view(torch.bool) if have_verts else None
-            out["cano_handle_sample_idx"] = (out["cano_handle_vert_idx"] if self.same
-                                             else own(self.surface_handle).view(torch.bool))
-            if with_inputs:
-                out["surface_samples_inputs"] = torch.cat([self.surface, self.buf[:, :, 3:7]], dim=-1)
+        out = {"verts_tgt_pred": own_pred(pred["verts_tgt_pred"])}
+        out["surface_samples_tgt_pred"] = (out["verts_tgt_pred"] if self.same
+                                           else own_pred(pred["surface_samples_tgt_pred"]))
+        out["verts_tgt"] = own(self.verts_tgt) if have_verts else None
+        out["cano_handle_vert_idx"] = own(self.verts_handle).view(torch.bool) if have_verts else None
+        out["cano_handle_sample_idx"] = (out["cano_handle_vert_idx"] if self.same
+                                         else own(self.surface_handle).view(torch.bool))
+        if with_inputs:
+            out["surface_samples_inputs"] = torch.cat([self.surface, self.buf[:, :, 3:7]], dim=-1)
         return out
-
-    # ------------------------------------------------------------------ the end
-    def _drop_graphs(self):
-        for step in self._steps.values():
-            step.close()
-        self._steps = {}
-
-    def close(self):
-        self._drop_graphs()
-        self.geometry = self.buf = self._surf_idx = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
 
 
 # ------------------------------------------------------------------------------------------- a packed batch of different meshes
 def ragged_refusal(model, verts_src, surface=None, cano=None, surface_cano=None):
     """Why a RaggedEditSession cannot be opened on these arguments (None: it can), each reason named."""
     import torch
-    from . import hip_decoder, precision
-    from .model.deformation_networks import Deformation_Networks
-    from .model.flow_arbitrary import FlowArbitrary
+    from . import hip_decoder
     from .ragged import RaggedPoints
-    if isinstance(model, FlowArbitrary):
-        nets = [model.model_canonicalize, model.model_deform]
-    elif isinstance(model, Deformation_Networks):
-        nets = [model]
-    else:
-        return f"the model must be a FlowArbitrary or a Deformation_Networks, got {type(model).__name__}"
-    if model.training or any(m.training for m in model.modules()):
-        return ("the model is in training mode: a session caches network 1's outputs and replays frozen weights, BatchNorm "
-                "would take batch statistics -- call model.eval() first")
-    if torch.is_grad_enabled():
-        return ("autograd is enabled: a session runs the inference kernels over cached tensors and records no graph -- open it "
-                "and drag under torch.no_grad()")
+    nets = _networks_or_refusal(model)
+    if isinstance(nets, str):
+        return nets
     if not isinstance(verts_src, RaggedPoints):
         return (f"verts_src must be a RaggedPoints (B meshes packed), got {type(verts_src).__name__} -- EditSession takes a "
                 "rectangular [B, V, 3] tensor")
@@ -386,14 +429,9 @@ def ragged_refusal(model, verts_src, surface=None, cano=None, surface_cano=None)
     for name, t in given.items():
         if (isinstance(t, RaggedPoints) or torch.is_tensor(t)) and not t.is_cuda:
             return f"CPU tensors: {name} is on the CPU -- the session's kernels have no CPU path"
-    if precision.is_bf16():
-        return "bf16 storage (NSDP_STORAGE=bf16): the session is built and tested in fp32 storage only"
-    net2 = nets[-1]
-    if net2.no_input_corr:
-        return "this network does not read the handle columns (no_input_corr: a backward-type network): a drag would change nothing"
-    if not (hasattr(net2.encoder, "geometry") and hasattr(net2.encoder, "ragged_geometry") and hasattr(net2.decoder, "geometry")):
-        return (f"the {type(net2.encoder).__name__} / {type(net2.decoder).__name__} pair has no geometry(): it searches inside "
-                "its forward pass only, so its index sets cannot be cached across drags")
+    why = _network_refusal(nets[-1], ("geometry", "ragged_geometry"))
+    if why is not None:
+        return why
     for net in nets:      # (what encoding a packed cloud and decoding a packed query set refuse, by their own names)
         why = net.ragged_surface_refusal() if isinstance(surface, RaggedPoints) or surface is None else (
             hip_decoder.ragged_refusal(net.decoder) if hip_decoder.supported(net.decoder) else
@@ -445,7 +483,7 @@ def ragged_refusal(model, verts_src, surface=None, cano=None, surface_cano=None)
     return None
 
 
-class RaggedEditSession:
+class RaggedEditSession(_Session):
     """An EditSession over a PACKED batch of B meshes of different vertex counts (nsdp_amd.ragged) -- the reference's batch loop
     over its user-handle data set, where the cloud network 2 encodes is each mesh's own vertex set.  Opened once, it holds network
     1's outputs, network 2's index sets (Deformation_Networks.ragged_geometry) and the per-shape bounding boxes; a drag is one
@@ -460,20 +498,12 @@ class RaggedEditSession:
     The predictions are bit-equal to the step function on the ragged data_dict the drag stands for
     (tests/test_edit_session_ragged_gpu.py).  Staleness: as for EditSession -- ``reopen()`` after the weights changed."""
 
-    def __init__(self, model, verts_src, surface=None, cano=None, surface_cano=None, partial_range=0.1, cliptail=False,
-                 graph=False, max_streams=None):
-        why = ragged_refusal(model, verts_src, surface, cano, surface_cano)
-        if why is not None:
-            raise ValueError("RaggedEditSession refused: " + why)
+    _refusal = staticmethod(ragged_refusal)
+    _cached = ("geometry", "buf", "inputs", "_vert_idx")
+
+    def _hold(self, verts_src, surface, cano, surface_cano):
         import torch
-        from . import query_shard
-        from .model.flow_arbitrary import FlowArbitrary
         from .ragged import RaggedPoints
-        self.model = model
-        self.flow = isinstance(model, FlowArbitrary)
-        self.net = model.model_deform if self.flow else model
-        for net in ([model.model_canonicalize, self.net] if self.flow else [self.net]):
-            query_shard.require_supported(net)      # (one decode standing for two: every query row on its own)
         tight = lambda r: RaggedPoints(r.packed.contiguous(), r.offsets, r.counts)      # (the host counts: read once, here)
         self.verts = tight(verts_src)
         self.same = surface is None
@@ -484,11 +514,10 @@ class RaggedEditSession:
             self.surface_rule = self.verts_rule if self.same else self.surface
         else:
             self.surface_rule = surface_cano.contiguous() if self.rect else tight(surface_cano)
-        self.partial_range, self.cliptail = float(partial_range), bool(cliptail)
-        self.graph, self.max_streams = bool(graph), max_streams
-        self.replays = self.eager_calls = 0
-        self._steps = {}
-        self._open()
+
+    def _layout(self):
+        cloud_rows = tuple(self.surface.shape[:2]) if self.rect else (self.surface.capacity,)
+        return self.verts.batch, self.verts.packed, cloud_rows, (self.verts.capacity,)
 
     # ------------------------------------------------------------------ the cached state
     def _open(self):
@@ -540,15 +569,6 @@ class RaggedEditSession:
                 self.verts_handle = torch.zeros((vcap,), dtype=torch.uint8, device=dev)
                 self._vrows = torch.empty((vcap, 7), dtype=torch.float32, device=dev)      # (the kernel's required output)
 
-    def reopen(self):
-        """Recompute everything the session caches (after the weights changed) and drop the captured graphs."""
-        why = ragged_refusal(self.model, self.verts, None if self.same else self.surface)
-        if why is not None:
-            raise ValueError("RaggedEditSession refused: " + why)
-        self._drop_graphs()
-        self._open()
-        return self
-
     # ------------------------------------------------------------------ one drag
     def _enqueue(self, masks, vert_masks):
         """Everything of a drag that runs on the GPU behind the parameter copy: capturable, reads device tensors only."""
@@ -577,113 +597,29 @@ class RaggedEditSession:
             out["surface_samples_tgt_pred"] = pred if self.rect else pred.packed
         return out
 
-    def _mask_buffer(self, name, like_rows, value):
+    def _result(self, pred, own, own_pred, have_verts, with_inputs):
+        """``verts_tgt_pred``, ``verts_tgt`` and ``cano_handle_vert_idx`` as RaggedPoints over the vertices' offsets (the handle
+        as [cap, 1] bool rows), ``surface_samples_tgt_pred`` and ``cano_handle_sample_idx`` over the cloud's layout (the same
+        objects when the cloud is the vertex set), and with ``with_inputs`` ``surface_samples_inputs``: a RaggedPoints of
+        [scap, 7] rows (or [B, S, 7]) the step function takes as it is."""
         import torch
-        buf = getattr(self, name)
-        if buf is None:
-            buf = torch.empty(like_rows, dtype=torch.uint8, device=self.verts.device)
-            setattr(self, name, buf)
-        if not torch.is_tensor(value) or not value.is_cuda:
-            raise ValueError("RaggedEditSession refused: CPU tensors: the masks of a drag must be GPU tensors")
-        if value.dtype not in (torch.bool, torch.uint8) or tuple(value.shape) != tuple(like_rows):
-            raise ValueError(f"drag: a mask must be bool / uint8 {tuple(like_rows)}, got {value.dtype} {tuple(value.shape)}")
-        buf.copy_(value, non_blocking=True)
-
-    def drag(self, part=None, translation=(0.0, 0.0, 0.0), handle_mask=None, move_mask=None, vert_handle_mask=None,
-             vert_move_mask=None, partial_range=None, cliptail=None, with_inputs=False, clone=True):
-        """One drag of every shape.  By rule: ``part`` (a name of PARTS, one per shape, or a HandleSpec) moves by ``translation``
-        ((dx, dy, dz) or [B, 3]).  By explicit regions: ``handle_mask`` / ``move_mask`` over the cloud -- packed (scap,) bool /
-        uint8 on the GPU, [B, S] for a rectangular cloud -- replace the rule; with a separate cloud ``vert_handle_mask`` /
-        ``vert_move_mask`` (cap,) do so for the vertices (without them ``verts_tgt`` and ``cano_handle_vert_idx`` are None).
-
-        Returns ``verts_tgt_pred``, ``verts_tgt`` and ``cano_handle_vert_idx`` as RaggedPoints over the vertices' offsets
-        (the handle as [cap, 1] bool rows), ``surface_samples_tgt_pred`` and ``cano_handle_sample_idx`` over the cloud's layout
-        (the same objects when the cloud is the vertex set), and with ``with_inputs`` ``surface_samples_inputs``: a RaggedPoints
-        of [scap, 7] rows (or [B, S, 7]) the step function takes as it is.  The tensors are the caller's own; ``clone=False``
-        hands out the session's buffers, overwritten by the next drag."""
-        import torch
-        from ._lib import on_device
-        if torch.is_grad_enabled():
-            raise ValueError("RaggedEditSession refused: autograd is enabled -- drag under torch.no_grad()")
-        if self.model.training:
-            raise ValueError("RaggedEditSession refused: the model is in training mode -- call model.eval() (and reopen() if "
-                             "the weights changed)")
-        if isinstance(part, HandleSpec):
-            spec, part, translation = part, part.part, part.translation
-            partial_range = spec.partial_range if partial_range is None else partial_range
-            cliptail = spec.cliptail if cliptail is None else cliptail
-        masks = handle_mask is not None or move_mask is not None
-        B = self.verts.batch
-        if masks:
-            if handle_mask is None or move_mask is None or part is not None:
-                raise ValueError("drag: handle_mask and move_mask go together and replace `part`")
-            if (vert_handle_mask is None) != (vert_move_mask is None) or (self.same and vert_handle_mask is not None):
-                raise ValueError("drag: vert_handle_mask and vert_move_mask go together, with a separate cloud only")
-            part = 0
-        elif part is None:
-            raise ValueError(f"drag: name the part that moves (one of {PARTS}) or give handle_mask and move_mask")
-        elif vert_handle_mask is not None or vert_move_mask is not None:
-            raise ValueError("drag: vertex masks go with handle_mask and move_mask")
-        vert_masks = masks and vert_handle_mask is not None
-        words = pack_params(B, part, translation, self.partial_range if partial_range is None else partial_range,
-                            self.cliptail if cliptail is None else cliptail)
-        with on_device(self.verts.packed):
-            # the one host-to-device copy of a drag, stream-ordered in front of the kernels that read it
-            self.params.copy_(torch.from_numpy(words), non_blocking=True)
-            if masks:
-                rows = tuple(self.surface.shape[:2]) if self.rect else (self.surface.capacity,)
-                self._mask_buffer("_mask_h", rows, handle_mask)
-                self._mask_buffer("_mask_m", rows, move_mask)
-                if vert_masks:
-                    self._mask_buffer("_vmask_h", (self.verts.capacity,), vert_handle_mask)
-                    self._mask_buffer("_vmask_m", (self.verts.capacity,), vert_move_mask)
-            key = (masks, vert_masks)
-            if self.graph:
-                if key not in self._steps:
-                    from .graph_step import GraphedStep
-                    self._steps[key] = GraphedStep(lambda: self._enqueue(*key), self.max_streams,
-                                                   weights_change=False).capture(warmup=1)
-                self.replays += 1
-                pred = self._steps[key]()
+        over_cloud = (lambda t: t) if self.rect else self.surface.like
+        out = {"verts_tgt_pred": self.verts.like(own_pred(pred["verts_tgt_pred"]))}
+        out["surface_samples_tgt_pred"] = (out["verts_tgt_pred"] if self.same
+                                           else over_cloud(own_pred(pred["surface_samples_tgt_pred"])))
+        out["verts_tgt"] = self.verts.like(own(self.verts_tgt)) if have_verts else None
+        out["cano_handle_vert_idx"] = self.verts.like(own(self.verts_handle).view(torch.bool).unsqueeze(-1)) if have_verts else None
+        if self.same:
+            out["cano_handle_sample_idx"] = out["cano_handle_vert_idx"]
+        else:
+            h = own(self.surface_handle).view(torch.bool)
+            out["cano_handle_sample_idx"] = h if self.rect else self.surface.like(h.unsqueeze(-1))
+        if with_inputs:
+            if self.rect:
+                out["surface_samples_inputs"] = torch.cat([self.surface, self.buf[:, :, 3:7]], dim=-1)
             else:
-                self.eager_calls += 1
-                pred = self._enqueue(*key)
-            own = (lambda t: t.clone()) if clone else (lambda t: t)      # the session's buffers: the next drag overwrites them
-            own_pred = own if self.graph else (lambda t: t)              # (an eager drag's predictions are fresh tensors)
-            over_cloud = (lambda t: t) if self.rect else self.surface.like
-            out = {"verts_tgt_pred": self.verts.like(own_pred(pred["verts_tgt_pred"]))}
-            out["surface_samples_tgt_pred"] = (out["verts_tgt_pred"] if self.same
-                                               else over_cloud(own_pred(pred["surface_samples_tgt_pred"])))
-            have_verts = self.same or not masks or vert_masks
-            out["verts_tgt"] = self.verts.like(own(self.verts_tgt)) if have_verts else None
-            out["cano_handle_vert_idx"] = self.verts.like(own(self.verts_handle).view(torch.bool).unsqueeze(-1)) if have_verts else None
-            if self.same:
-                out["cano_handle_sample_idx"] = out["cano_handle_vert_idx"]
-            else:
-                h = own(self.surface_handle).view(torch.bool)
-                out["cano_handle_sample_idx"] = h if self.rect else self.surface.like(h.unsqueeze(-1))
-            if with_inputs:
-                if self.rect:
-                    out["surface_samples_inputs"] = torch.cat([self.surface, self.buf[:, :, 3:7]], dim=-1)
-                else:
-                    out["surface_samples_inputs"] = self.surface.like(torch.cat([self.surface.packed, self.buf[:, 3:7]], dim=-1))
+                out["surface_samples_inputs"] = self.surface.like(torch.cat([self.surface.packed, self.buf[:, 3:7]], dim=-1))
         return out
-
-    # ------------------------------------------------------------------ the end
-    def _drop_graphs(self):
-        for step in self._steps.values():
-            step.close()
-        self._steps = {}
-
-    def close(self):
-        self._drop_graphs()
-        self.geometry = self.buf = self.inputs = self._vert_idx = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
 
 
 def reference_data_dict(verts_src, surface, spec_or_params, cano=None, surface_cano=None):
@@ -792,44 +728,28 @@ def counts_from_args(args):
     return verts, surf
 
 
-def main_ragged(args, vertex_counts, surface_counts):
-    """--vertex-counts: the packed session on synthetic meshes, timed against the parent's two alternatives -- the ragged step
-    function per drag, and one batch-1 EditSession per mesh dragged in turn."""
+def _setup(args, smallest_cloud):
+    """What both forms of the command line do first: the thread cap, the GPU, the config and its drag, the pyramid cut to the
+    smallest cloud, the model (procedural weights without --weight_file) -- and the two helpers of the timed windows."""
     from .cpu_budget import cap_thread_pools
     cap_thread_pools(16)
-    import numpy as np
     import torch
     if not torch.cuda.is_available():
         sys.exit("nsdp_amd.edit: needs a GPU (the session has no CPU path)")
     device = torch.device("cuda", 0)
     torch.cuda.set_device(0)
-    from . import pointnet2_utils, synth
+    from . import synth
     from .config import load_config
-    from .infer import _checksum, _pyramid
+    from .infer import _pyramid
     from .model import build_model
-    from .ragged import RaggedPoints
     config = load_config(args.config_file)
     spec = spec_from_args(args, config)
-    B = len(vertex_counts)
-    cloud_counts = surface_counts or ([args.surface] * B if args.surface else vertex_counts)
-    _pyramid(config, min(cloud_counts))
+    _pyramid(config, smallest_cloud)
     model, _, _, test_fn = build_model(config, weight_file=args.weight_file, device="cpu")
     if args.weight_file is None:
         state = synth.procedural_state_dict(model.state_dict(), SEED_WEIGHTS)
         model.load_state_dict({k: torch.from_numpy(v) for k, v in state.items()})
     model.to(device).eval()
-    meshes = [torch.from_numpy(synth.uniform(SEED_DATA + b, "mesh_verts", (1, n, 3), -0.5, 0.5)).to(device)
-              for b, n in enumerate(vertex_counts)]
-    verts = RaggedPoints.from_list([m[0] for m in meshes])
-    clouds, surface = None, None
-    if surface_counts is not None:
-        clouds = [torch.from_numpy(synth.uniform(SEED_DATA + b, "mesh_surface", (1, n, 3), -0.5, 0.5)).to(device)
-                  for b, n in enumerate(surface_counts)]
-        surface = RaggedPoints.from_list([c[0] for c in clouds])
-    elif args.surface is not None:
-        clouds = [torch.from_numpy(synth.uniform(SEED_DATA + b, "mesh_surface", (1, args.surface, 3), -0.5, 0.5)).to(device)
-                  for b in range(B)]
-        surface = torch.cat(clouds, dim=0)
 
     def timed(fn, n=1):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -843,6 +763,33 @@ def main_ragged(args, vertex_counts, surface_counts):
 
     def translation(i):      # (another drag every time: nothing of a previous one can be reused)
         return tuple(v * (1.0 + 0.01 * i) for v in spec.translation)
+
+    return device, config, spec, model, test_fn, timed, translation
+
+
+def main_ragged(args, vertex_counts, surface_counts):
+    """--vertex-counts: the packed session on synthetic meshes, timed against the parent's two alternatives -- the ragged step
+    function per drag, and one batch-1 EditSession per mesh dragged in turn."""
+    B = len(vertex_counts)
+    cloud_counts = surface_counts or ([args.surface] * B if args.surface else vertex_counts)
+    device, config, spec, model, test_fn, timed, translation = _setup(args, min(cloud_counts))
+    import numpy as np
+    import torch
+    from . import pointnet2_utils, synth
+    from .infer import _checksum
+    from .ragged import RaggedPoints
+    meshes = [torch.from_numpy(synth.uniform(SEED_DATA + b, "mesh_verts", (1, n, 3), -0.5, 0.5)).to(device)
+              for b, n in enumerate(vertex_counts)]
+    verts = RaggedPoints.from_list([m[0] for m in meshes])
+    clouds, surface = None, None
+    if surface_counts is not None:
+        clouds = [torch.from_numpy(synth.uniform(SEED_DATA + b, "mesh_surface", (1, n, 3), -0.5, 0.5)).to(device)
+                  for b, n in enumerate(surface_counts)]
+        surface = RaggedPoints.from_list([c[0] for c in clouds])
+    elif args.surface is not None:
+        clouds = [torch.from_numpy(synth.uniform(SEED_DATA + b, "mesh_surface", (1, args.surface, 3), -0.5, 0.5)).to(device)
+                  for b in range(B)]
+        surface = torch.cat(clouds, dim=0)
 
     warm = max(args.warmup, 1)
     with torch.no_grad():
@@ -904,44 +851,15 @@ def main(argv=None):
         return main_ragged(args, vertex_counts, surface_counts)
     if args.vertices < 1 or (args.surface is not None and args.surface < 1) or args.drags < 1:
         sys.exit("nsdp_amd.edit: --vertices, --surface and --drags want positive integers")
-    from .cpu_budget import cap_thread_pools
-    cap_thread_pools(16)
+    device, config, spec, model, test_fn, timed, translation = _setup(args, args.surface or args.vertices)
     import numpy as np
     import torch
-    if not torch.cuda.is_available():
-        sys.exit("nsdp_amd.edit: needs a GPU (the session has no CPU path)")
-    device = torch.device("cuda", 0)
-    torch.cuda.set_device(0)
     from . import pointnet2_utils, synth
-    from .config import load_config
-    from .infer import _checksum, _pyramid
-    from .model import build_model
-    config = load_config(args.config_file)
-    spec = spec_from_args(args, config)
+    from .infer import _checksum
     batch = args.batch or int((config.get("test") or {}).get("batch_size", 1) or 1)
-    _pyramid(config, args.surface or args.vertices)
-    model, _, _, test_fn = build_model(config, weight_file=args.weight_file, device="cpu")
-    if args.weight_file is None:
-        state = synth.procedural_state_dict(model.state_dict(), SEED_WEIGHTS)
-        model.load_state_dict({k: torch.from_numpy(v) for k, v in state.items()})
-    model.to(device).eval()
     verts = torch.from_numpy(synth.uniform(SEED_DATA, "mesh_verts", (batch, args.vertices, 3), -0.5, 0.5)).to(device)
     surface = None if args.surface is None else \
         torch.from_numpy(synth.uniform(SEED_DATA, "mesh_surface", (batch, args.surface, 3), -0.5, 0.5)).to(device)
-
-    def timed(fn, n=1):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize()
-        e0.record()
-        for i in range(n):
-            fn(i)
-        e1.record()
-        torch.cuda.synchronize()
-        return e0.elapsed_time(e1) / max(1, n)
-
-    def translation(i):      # (another drag every time: nothing of a previous one can be reused)
-        return tuple(v * (1.0 + 0.01 * i) for v in spec.translation)
-
     with torch.no_grad():
         box = {}
         timed(lambda i: box.update(s=EditSession(model, verts, surface, partial_range=spec.partial_range, cliptail=spec.cliptail,

@@ -493,8 +493,9 @@ def scatter_add_rows(grad_out: torch.Tensor, idx: torch.Tensor, N: int) -> torch
     return out
 
 
-# User-handle drags (include/nsdp_handles.h, csrc/handles.hip): the bounding box of a cloud, and the handle rule + dragged target
-# + columns 3..6 of the deformation network's input rows, with the drag parameters in device memory (nsdp_amd.edit).
+# User-handle drags (include/nsdp_handles.h, csrc/handles.hip; the rule itself: csrc/handles_rule.h): the bounding box of a
+# cloud, and the handle rule + dragged target + columns 3..6 of the deformation network's input rows, with the drag parameters in
+# device memory (nsdp_amd.edit).
 HANDLE_PARTS = ("head", "tail", "frontleftfoot", "frontrightfoot", "behindleftfoot", "behindrightfoot")      # NSDP_HANDLE_* order
 HANDLE_PARAM_WORDS = 8
 HANDLE_MAX_POINTS = 1 << 20
@@ -517,6 +518,21 @@ def _bytes_ptr(t, name, shape):
     return ctypes.c_void_p(t.data_ptr())
 
 
+def _bounds_buffers(who, need, B, device, workspace, out, refused):
+    """The workspace and the (B,6) output of a bounds entry (``who``): the caller's, checked, or allocated here.  ``need``: the
+    entry's workspace bytes, 0 when it refuses the sizes -- then ``refused`` says which."""
+    if need == 0:
+        raise _lib.NsdpHipError(f"{who}: {refused}")
+    if workspace is None:
+        workspace = torch.empty((need // 4,), dtype=torch.int32, device=device)
+    elif not (workspace.is_cuda and workspace.is_contiguous() and workspace.numel() * workspace.element_size() >= need):
+        raise _lib.NsdpHipError(f"{who}: the workspace must be a contiguous GPU tensor of at least {need} bytes")
+    bounds = torch.empty((B, 6), dtype=torch.float32, device=device) if out is None else out
+    if tuple(bounds.shape) != (B, 6):
+        raise _lib.NsdpHipError(f"{who}: out must be ({B}, 6), got {tuple(bounds.shape)}")
+    return workspace, bounds
+
+
 def handle_bounds(cano: torch.Tensor, workspace=None, out=None) -> torch.Tensor:
     """Per-shape bounding box (nsdp_handle_bounds): cano (B,n,3) fp32 -> (B,6) fp32, min xyz then max xyz, the exact extremes
     (-0.0 sorts below +0.0).  ``workspace``: a buffer of the caller's, else allocated here; ``out``: a (B,6) buffer."""
@@ -526,15 +542,8 @@ def handle_bounds(cano: torch.Tensor, workspace=None, out=None) -> torch.Tensor:
         fn = lib().nsdp_handle_bounds_workspace_bytes
         fn.restype = ctypes.c_size_t
         need = int(fn(_c_int(B), _c_int(n)))
-        if need == 0:
-            raise _lib.NsdpHipError(f"handle_bounds: B={B} shapes of n={n} points outside 1..65535 x 1..{HANDLE_MAX_POINTS}")
-        if workspace is None:
-            workspace = torch.empty((need // 4,), dtype=torch.int32, device=cano.device)
-        elif not (workspace.is_cuda and workspace.is_contiguous() and workspace.numel() * workspace.element_size() >= need):
-            raise _lib.NsdpHipError(f"handle_bounds: the workspace must be a contiguous GPU tensor of at least {need} bytes")
-        bounds = torch.empty((B, 6), dtype=torch.float32, device=cano.device) if out is None else out
-        if tuple(bounds.shape) != (B, 6):
-            raise _lib.NsdpHipError(f"handle_bounds: out must be ({B}, 6), got {tuple(bounds.shape)}")
+        workspace, bounds = _bounds_buffers("handle_bounds", need, B, cano.device, workspace, out,
+                                            f"B={B} shapes of n={n} points outside 1..65535 x 1..{HANDLE_MAX_POINTS}")
         check(lib().nsdp_handle_bounds(fptr(cano, "cano"), _c_int(B), _c_int(n), optptr(workspace), fptr(bounds, "bounds"),
                                        stream_ptr()), "nsdp_handle_bounds")
     return bounds
@@ -592,16 +601,9 @@ def handle_bounds_ragged(cano: torch.Tensor, offsets: torch.Tensor, n_max: int, 
         fn = lib().nsdp_handle_bounds_ragged_workspace_bytes
         fn.restype = ctypes.c_size_t
         need = int(fn(_c_int(B), _c_int(cap), _c_int(n_max)))
-        if need == 0:
-            raise _lib.NsdpHipError(f"handle_bounds_ragged: B={B} shapes in cap={cap} rows with n_max={n_max} outside 1..65535, "
-                                    f"1.., 1..{HANDLE_MAX_POINTS}")
-        if workspace is None:
-            workspace = torch.empty((need // 4,), dtype=torch.int32, device=cano.device)
-        elif not (workspace.is_cuda and workspace.is_contiguous() and workspace.numel() * workspace.element_size() >= need):
-            raise _lib.NsdpHipError(f"handle_bounds_ragged: the workspace must be a contiguous GPU tensor of at least {need} bytes")
-        bounds = torch.empty((B, 6), dtype=torch.float32, device=cano.device) if out is None else out
-        if tuple(bounds.shape) != (B, 6):
-            raise _lib.NsdpHipError(f"handle_bounds_ragged: out must be ({B}, 6), got {tuple(bounds.shape)}")
+        workspace, bounds = _bounds_buffers("handle_bounds_ragged", need, B, cano.device, workspace, out,
+                                            f"B={B} shapes in cap={cap} rows with n_max={n_max} outside 1..65535, 1.., "
+                                            f"1..{HANDLE_MAX_POINTS}")
         check(lib().nsdp_handle_bounds_ragged(fptr(cano, "cano"), iptr(offsets, "offsets"), _c_int(B), _c_int(cap), _c_int(n_max),
                                               optptr(workspace), fptr(bounds, "bounds"), stream_ptr()), "nsdp_handle_bounds_ragged")
     return bounds

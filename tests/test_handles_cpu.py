@@ -52,7 +52,7 @@ def test_header_constants_mirror_the_python_side():
         assert re.search(rf"NSDP_HANDLE_{part.upper()} = {i}\b", text), part
     assert pu.HANDLE_PARTS == edit.PARTS
     assert f"NSDP_HANDLE_PARAM_WORDS = {pu.HANDLE_PARAM_WORDS}" in text
-    source = open(os.path.join(ROOT, "nsdp_amd", "csrc", "handles.hip")).read()
+    source = open(os.path.join(ROOT, "nsdp_amd", "csrc", "handles_rule.h")).read()      # (the limit of both layouts)
     assert "kMaxPoints = 1 << 20;" in source and pu.HANDLE_MAX_POINTS == 1 << 20
 
 
