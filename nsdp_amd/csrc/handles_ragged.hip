@@ -1,7 +1,8 @@
 // User-handle drags over a packed batch of meshes of different sizes (include/nsdp_handles_ragged.h).  This file is the PACKED
 // layout: each shape's rows are read from offsets(B+1) on the device instead of a rectangle.  What a workgroup does with its
-// shape's rows and what a lane does with its row is handles_rule.h, the text handles.hip runs; here are the offsets -- a shape's
-// clamped range, a row's owner -- the two kernels that name the rows, the argument checks and the launches.
+// shape's rows and what a lane does with its row is handles_rule.h, the text handles.hip runs; the offsets -- a shape's clamped
+// range, a row's owner -- are packed_rows.h, shared with handle_sets.hip; here are the two kernels that name the rows, the
+// argument checks and the launches.
 //
 //   bounds   partial: grid (G, B), G = ceil(n_max / kPointsPerGroup).  Workgroup (g, b) reads shape b's range from the offsets
 //            and reduces its share to six keys; where its share is empty (a short or an empty shape) the keys it writes are the
@@ -14,20 +15,13 @@
 // Built with -ffp-contract=off, as handles_rule.h requires: a row carries the bits the rectangular entry gives it on its shape
 // alone because both files compile one text of the rule under one flag.
 #include "handles_rule.h"
+#include "packed_rows.h"      // a shape's clamped range, a row's owner
 
 namespace {
 
 inline bool refused(int B, int cap, int n_max) { return B < 1 || B > 65535 || cap < 1 || n_max < 1 || n_max > kMaxPoints; }
 
 inline int groups_of(int n_max) { return nsdp::ceil_div(n_max, kPointsPerGroup); }
-
-__device__ __forceinline__ int clamped(int v, int lo, int hi) { return min(max(v, lo), hi); }
-
-// Rows [first, end) of shape b (0 <= b < B): 0 <= first <= end <= cap whatever `offsets` holds.
-__device__ __forceinline__ void shape_range(const int32_t *__restrict__ offsets, int b, int cap, int &first, int &end) {
-  first = clamped(offsets[b], 0, cap);
-  end = clamped(offsets[b + 1], first, cap);
-}
 
 __global__ __launch_bounds__(kThreads) void handle_bounds_ragged_partial_kernel(const float *__restrict__ cano,
                                                                                 const int32_t *__restrict__ offsets, int cap,
@@ -40,23 +34,6 @@ __global__ __launch_bounds__(kThreads) void handle_bounds_ragged_partial_kernel(
                  part_all + (static_cast<long long>(b) * G + g) * 6);
 }
 
-// The shape that owns packed row p: the last b in [0, B) whose clamped first row is <= p, if p is below that shape's clamped
-// end.  Binary search for the first j in [1, B] with offsets[j] > p (B <= 65535: at most 16 steps).  false: no shape owns p.
-__device__ __forceinline__ bool owner_of(const int32_t *__restrict__ offsets, int B, int cap, int p, int &b, int &first, int &end) {
-  int lo = 1, hi = B + 1;
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (clamped(offsets[mid], 0, cap) > p)
-      hi = mid;
-    else
-      lo = mid + 1;
-  }
-  if (lo > B) return false;      // p is at or beyond offsets[B]
-  b = lo - 1;
-  shape_range(offsets, b, cap, first, end);
-  return p >= first && p < end;
-}
-
 template <bool MASKS>
 __global__ __launch_bounds__(kThreads) void handle_rows_ragged_kernel(
     const float *__restrict__ cano_all, const float *__restrict__ src_all, const int32_t *__restrict__ offsets,
@@ -65,13 +42,8 @@ __global__ __launch_bounds__(kThreads) void handle_rows_ragged_kernel(
     uint8_t *__restrict__ handle_out, uint8_t *__restrict__ move_out) {
   const long long p = static_cast<long long>(blockIdx.x) * kThreads + threadIdx.x;
   if (p >= cap) return;
-  // the wave's first row (always below cap here: lane 0 is the wave's lowest row), looked up with uniform loads
-  const int p0 = __builtin_amdgcn_readfirstlane(static_cast<int>(p));
-  int b = 0, first = 0, end = 0;
-  bool owned = owner_of(offsets, B, cap, p0, b, first, end);
-  b = __builtin_amdgcn_readfirstlane(b);
-  if (!owned || p >= end) owned = owner_of(offsets, B, cap, static_cast<int>(p), b, first, end);
-  if (!owned) return;
+  int b;
+  if (!owner_of_lane(offsets, B, cap, p, b)) return;
   handle_row<MASKS>(p, b, cano_all, src_all, bounds_all, params_all, handle_mask, move_mask, rows_all, tgt_all, handle_out, move_out);
 }
 

@@ -38,6 +38,18 @@ mesh's own vertex set -- goes through a ``RaggedEditSession`` over packed sets (
     s = RaggedEditSession(model, RaggedPoints.from_list([v0, v1, v2]))
     out = s.drag(part=["head", "tail", "head"], translation=(-0.15, -0.2, -0.2))      # RaggedPoints come back
 
+Several handles at once, each with a motion of its own -- turn the head, lift a paw, pin the other feet -- go through a labelled
+handle set on either session class (include/nsdp_handle_sets.h): a byte per point names its handle, a pose gives every handle a
+3 x 4 motion (``Motion``: translate, rotate about a pivot, affine, composed on the host) or every point a target:
+
+    labels, count = s.labels_from_parts(["head", "frontleftfoot"])      # or any uint8 labels of the caller's
+    s.set_handles(labels, count)
+    out = s.pose(motions=[Motion.rotate((0, 0, 1), 20, pivot=c), Motion.translate((0, 0, 0.1)), Motion.identity()])
+    out = s.pose(targets=recorded_frame)                                # [B, n, 3]: read at the handle points
+    out = s.track(motions=[pose_1, ..., pose_T])                        # EditSession: T poses, one pass over T * B rows
+
+    python -m nsdp_amd.edit CONFIG --handles head,frontleftfoot [--rotate-deg 20 --axis 0,0,1] [--translate dx,dy,dz] [--track T]
+
 Every stage of a drag is the kernel the step function runs, on the same operands: the predictions are bit-equal to
 ``test_on_batch_with_arbitrary`` (``test_on_batch_with_cano`` for a single network) on the data_dict the drag stands for
 (tests/test_edit_session_gpu.py, tests/test_edit_session_ragged_gpu.py).
@@ -107,6 +119,116 @@ def pack_params(B, part, translation, partial_range, cliptail):
     f[:, 2] = np.broadcast_to(np.asarray(partial_range, dtype=np.float32), (B,))
     f[:, 3:6] = np.broadcast_to(d, (B, 3))
     return words
+
+
+class Motion:
+    """x -> A x + t, what one handle does in a pose (include/nsdp_handle_sets.h): composed on the host in float64 and rounded
+    ONCE to float32, by ``matrix()``.  A rotation about a pivot c is [R | c - R c]: the pivot is folded into t here, where float64
+    is free, so the kernel's arithmetic stays three products and three sums per coordinate for every kind of motion."""
+    __slots__ = ("m",)
+
+    def __init__(self, m):
+        import numpy as np
+        a = np.array(m, dtype=np.float64)
+        if a.shape == (12,):
+            a = a.reshape(3, 4)
+        if a.shape != (3, 4):
+            raise ValueError(f"Motion: a 3 x 4 matrix [A | t] (or its 12 numbers, row-major), got shape {a.shape}")
+        self.m = a
+
+    @classmethod
+    def identity(cls):
+        """A pinned handle: its points are handle points whose target is where they are."""
+        import numpy as np
+        return cls(np.eye(3, 4))
+
+    @classmethod
+    def translate(cls, d):
+        import numpy as np
+        m = np.eye(3, 4)
+        m[:, 3] = np.asarray(d, dtype=np.float64).reshape(3)
+        return cls(m)
+
+    @classmethod
+    def affine(cls, A, t=(0.0, 0.0, 0.0)):
+        import numpy as np
+        return cls(np.concatenate([np.asarray(A, dtype=np.float64).reshape(3, 3), np.asarray(t, dtype=np.float64).reshape(3, 1)], axis=1))
+
+    @classmethod
+    def rotate(cls, axis, degrees, pivot=(0.0, 0.0, 0.0)):
+        """By ``degrees`` about the line through ``pivot`` along ``axis`` (right-handed; any non-zero length)."""
+        import numpy as np
+        a = np.asarray(axis, dtype=np.float64).reshape(3)
+        norm = float(np.linalg.norm(a))
+        if not norm > 0.0 or not np.isfinite(norm):
+            raise ValueError(f"Motion.rotate: the axis must have a finite non-zero length, got {tuple(a)}")
+        a = a / norm
+        quarter = float(degrees) / 90.0
+        if quarter == round(quarter):      # whole quarter turns: cosine and sine are exactly 0, 1 or -1
+            c, s = ((1.0, 0.0), (0.0, 1.0), (-1.0, 0.0), (0.0, -1.0))[int(round(quarter)) % 4]
+        else:
+            c, s = float(np.cos(np.radians(float(degrees)))), float(np.sin(np.radians(float(degrees))))
+        K = np.array([[0.0, -a[2], a[1]], [a[2], 0.0, -a[0]], [-a[1], a[0], 0.0]])
+        R = c * np.eye(3) + s * K + (1.0 - c) * np.outer(a, a)
+        p = np.asarray(pivot, dtype=np.float64).reshape(3)
+        return cls.affine(R, p - R @ p)
+
+    def then(self, other):
+        """This motion first, ``other`` after it."""
+        import numpy as np
+        A = other.m[:, :3] @ self.m[:, :3]
+        t = other.m[:, :3] @ self.m[:, 3] + other.m[:, 3]
+        return Motion(np.concatenate([A, t.reshape(3, 1)], axis=1))
+
+    def matrix(self):
+        """[3, 4] float32: the one rounding."""
+        import numpy as np
+        return self.m.astype(np.float32)
+
+    def __repr__(self):
+        return f"Motion({self.m.tolist()})"
+
+
+def _motion12(m):
+    """One motion as 12 float32 numbers (a Motion, or (12,) / (3, 4) numbers); None if ``m`` is not one."""
+    import numpy as np
+    if isinstance(m, Motion):
+        return m.matrix().reshape(12)
+    try:
+        a = np.asarray(m, dtype=np.float64)
+    except (TypeError, ValueError):
+        return None
+    return a.astype(np.float32).reshape(12) if a.shape in ((12,), (3, 4)) else None
+
+
+def pack_motions(B, H, motions):
+    """The [B, H, 12] float32 host array the labelled kernel reads, row h - 1 of a shape = the motion of its label h.
+    ``motions``: one list of H motions (Motion, or 12 numbers) for every shape, a list of B such lists, or an array / tensor
+    that already is [B, H, 12] (or [B, H, 3, 4])."""
+    import numpy as np
+    if hasattr(motions, "detach"):
+        motions = motions.detach().cpu().numpy()
+    if isinstance(motions, np.ndarray) and motions.dtype != object:
+        if motions.shape in ((B, H, 12), (B, H, 3, 4)):
+            return np.ascontiguousarray(motions.reshape(B, H, 12), dtype=np.float32)
+        if motions.shape in ((H, 12), (H, 3, 4)):
+            return np.array(np.broadcast_to(motions.reshape(1, H, 12), (B, H, 12)), dtype=np.float32, order="C")      # (a copy: writable)
+        raise ValueError(f"pack_motions: an array of motions must be [{B}, {H}, 12] (B shapes, H handles), got {motions.shape}")
+    if isinstance(motions, (Motion, str)) or not hasattr(motions, "__len__"):
+        raise ValueError(f"pack_motions: a list of {H} motions, or one such list per shape, got {type(motions).__name__}")
+    rows = list(motions)
+    flat = [_motion12(m) for m in rows]
+    if len(rows) == H and all(f is not None for f in flat):
+        return np.array(np.broadcast_to(np.stack(flat)[None], (B, H, 12)), dtype=np.float32, order="C")      # (a copy: writable)
+    if len(rows) == B and all(hasattr(r, "__len__") and not isinstance(r, (Motion, str)) for r in rows):
+        out = np.empty((B, H, 12), dtype=np.float32)
+        for b, shape_motions in enumerate(rows):
+            per = [_motion12(m) for m in shape_motions]
+            if len(per) != H or any(p is None for p in per):
+                raise ValueError(f"pack_motions: shape {b} has {len(per)} motions for {H} handles, or one of them is no 3 x 4 motion")
+            out[b] = np.stack(per)
+        return out
+    raise ValueError(f"pack_motions: {len(rows)} entries are neither {H} motions (one per handle) nor {B} lists (one per shape)")
 
 
 def _networks_or_refusal(model):
@@ -189,6 +311,8 @@ class _Session:
       _layout()                                                 (B, the tensor that names the device, the shape of a mask over
                                                                 the cloud, of one over the vertices);
       _enqueue(masks, vert_masks)                               the GPU work of a drag behind the copies;
+      _enqueue_pose(targets, vert)                              the same for a pose of the labelled handle set (set_handles);
+      _rule_flags(verts, handle_out, move_out)                  the rule kernel for its flags alone (labels_from_parts);
       _result(pred, own, own_pred, have_verts, with_inputs)     the dict a drag returns;
       _cached                                                   the attributes close() lets go of."""
 
@@ -211,6 +335,7 @@ class _Session:
         self.graph, self.max_streams = bool(graph), max_streams
         self.replays = self.eager_calls = 0
         self._steps = {}
+        self._forget_handles()
         self._open()
 
     @property
@@ -223,6 +348,7 @@ class _Session:
         if why is not None:
             raise ValueError(self._refused + why)
         self._drop_graphs()
+        self._tracks = {}      # (a track holds index sets of its own; the labels and their count stay)
         self._open()
         return self
 
@@ -288,19 +414,156 @@ class _Session:
                     self._mask_buffer("_vmask_h", vert_rows, vert_handle_mask, on.device)
                     self._mask_buffer("_vmask_m", vert_rows, vert_move_mask, on.device)
             key = (masks, vert_masks)
-            if self.graph:
-                if key not in self._steps:
-                    from .graph_step import GraphedStep
-                    self._steps[key] = GraphedStep(lambda: self._enqueue(*key), self.max_streams,
-                                                   weights_change=False).capture(warmup=1)
-                self.replays += 1
-                pred = self._steps[key]()
-            else:
-                self.eager_calls += 1
-                pred = self._enqueue(*key)
-            own = (lambda t: t.clone()) if clone else (lambda t: t)      # the session's buffers: the next drag overwrites them
-            own_pred = own if self.graph else (lambda t: t)              # (an eager drag's predictions are fresh tensors)
+            pred = self._dispatch(key, lambda: self._enqueue(*key))
+            own, own_pred = self._owners(clone)
             return self._result(pred, own, own_pred, self.same or not masks or vert_masks, with_inputs)
+
+    def _dispatch(self, key, enqueue):
+        """The GPU work of one call behind its copies: op by op, or (``graph=True``) captured at the first call of this ``key``
+        and replayed from then on."""
+        if self.graph:
+            if key not in self._steps:
+                from .graph_step import GraphedStep
+                self._steps[key] = GraphedStep(enqueue, self.max_streams, weights_change=False).capture(warmup=1)
+            self.replays += 1
+            return self._steps[key]()
+        self.eager_calls += 1
+        return enqueue()
+
+    def _owners(self, clone):
+        own = (lambda t: t.clone()) if clone else (lambda t: t)      # the session's buffers: the next drag overwrites them
+        return own, (own if self.graph else (lambda t: t))           # (an eager drag's predictions are fresh tensors)
+
+    # ------------------------------------------------------------------ labelled handle sets
+    def _forget_handles(self):
+        self._labels = self._vlabels = self._motions = self._targets = self._vtargets = None
+        self._count, self._vert_labelled, self._tracks = 0, False, {}
+
+    def _drop_set_graphs(self):
+        for key in [k for k in self._steps if k[0] in ("pose", "track")]:
+            self._steps.pop(key).close()
+
+    def _session_tensor(self, value, shape, dtype, what):
+        """Refuses ``value`` unless it is a GPU tensor of ``shape`` and ``dtype``."""
+        import torch
+        if not torch.is_tensor(value):
+            raise ValueError(f"{what} must be a torch.Tensor, got {type(value).__name__}")
+        if not value.is_cuda:
+            raise ValueError(self._refused + f"CPU tensors: {what} must be a GPU tensor")
+        if value.dtype is not dtype or tuple(value.shape) != tuple(shape):
+            raise ValueError(f"{what} must be {str(dtype).replace('torch.', '')} {tuple(shape)}, got "
+                             f"{str(value.dtype).replace('torch.', '')} {tuple(value.shape)}")
+
+    def _session_copy(self, name, value):
+        """``value`` copied into the session's buffer ``name``, made at first use (the graphs read the buffer)."""
+        import torch
+        buf = getattr(self, name)
+        if buf is None:
+            buf = torch.empty_like(value, memory_format=torch.contiguous_format)
+            setattr(self, name, buf)
+        buf.copy_(value, non_blocking=True)
+
+    def set_handles(self, labels, count, vert_labels=None):
+        """The handle set the next poses move: ``labels`` uint8 on the GPU over the cloud ([B, n]; (scap,) for a packed cloud),
+        0 = a free point, h in 1..``count`` = a point of handle h (a larger label is a free point).  ``count`` = H is the
+        caller's, so nothing is read back.  ``vert_labels`` ([B, V]; packed (cap,)): the same for the vertices of a separate
+        cloud; without them ``verts_tgt`` and ``cano_handle_vert_idx`` come back None, as for drags by masks.  The labels are
+        copied.  Setting them again with the same ``count`` keeps the captured graphs of the poses."""
+        import torch
+        from ._lib import on_device
+        if isinstance(count, bool) or not isinstance(count, int) or not 1 <= count <= 255:
+            raise ValueError(f"set_handles: count must be an integer in 1..255 (the labels are bytes), got {count!r}")
+        B, on, cloud_rows, vert_rows = self._layout()
+        if vert_labels is not None and self.same:
+            raise ValueError("set_handles: vert_labels go with a separate cloud only (here the cloud is the vertex set)")
+        self._session_tensor(labels, cloud_rows, torch.uint8, "set_handles: labels")
+        if vert_labels is not None:
+            self._session_tensor(vert_labels, vert_rows, torch.uint8, "set_handles: vert_labels")
+        with on_device(on):
+            self._session_copy("_labels", labels)
+            self._vert_labelled = vert_labels is not None      # (the buffer stays: a captured graph reads it)
+            if self._vert_labelled:
+                self._session_copy("_vlabels", vert_labels)
+            if count != self._count:      # (the motion tables are [.., H, 12]: other kernel arguments)
+                self._drop_set_graphs()
+                self._tracks = {}
+                self._motions = torch.empty((B, count, 12), dtype=torch.float32, device=on.device)
+                self._count = count
+        return self
+
+    def _pose_checks(self, what, motions, targets, vert_targets):
+        import torch
+        if torch.is_grad_enabled():
+            raise ValueError(self._refused + f"autograd is enabled -- {what} under torch.no_grad()")
+        if self.model.training:
+            raise ValueError(self._refused + "the model is in training mode -- call model.eval() (and reopen() if the weights "
+                             "changed)")
+        if self._labels is None:
+            raise ValueError(f"{what} before set_handles: the session has no labelled handle set")
+        if (motions is None) == (targets is None):
+            raise ValueError(f"{what}: exactly one of motions and targets (got {'neither' if motions is None else 'both'})")
+        if vert_targets is not None:
+            if targets is None:
+                raise ValueError(f"{what}: vert_targets go with targets")
+            if not self._vert_labelled:
+                raise ValueError(f"{what}: vert_targets without vert_labels -- set_handles(labels, count, vert_labels) names the "
+                                 "vertices they belong to" + (" (here the cloud is the vertex set: targets are theirs)" if self.same else ""))
+        # the vertices' own rows: with a separate cloud, when their labels are set and this form has something to move them by
+        return not self.same and self._vert_labelled and (targets is None or vert_targets is not None)
+
+    def pose(self, motions=None, targets=None, vert_targets=None, with_inputs=False, clone=True):
+        """One pose of every shape's labelled handle set (``set_handles``).  ``motions``: anything ``pack_motions`` takes -- one
+        list of H motions for every shape, a list per shape, or a [B, H, 12] array; one host-to-device copy.  ``targets``: a
+        target per cloud point instead, a float32 GPU tensor over the cloud's layout with 3 columns ([B, n, 3]; (scap, 3)),
+        read at the handle points only; ``vert_targets`` the same for the vertices of a separate cloud.  Returns what ``drag``
+        returns, in the same shapes."""
+        import torch
+        from ._lib import on_device
+        vert = self._pose_checks("pose", motions, targets, vert_targets)
+        B, on, cloud_rows, vert_rows = self._layout()
+        if targets is None:
+            words = pack_motions(B, self._count, motions)
+        else:
+            self._session_tensor(targets, cloud_rows + (3,), torch.float32, "pose: targets")
+            if vert:
+                self._session_tensor(vert_targets, vert_rows + (3,), torch.float32, "pose: vert_targets")
+        with on_device(on):
+            if targets is None:
+                self._motions.copy_(torch.from_numpy(words), non_blocking=True)
+            else:
+                self._session_copy("_targets", targets)
+                if vert:
+                    self._session_copy("_vtargets", vert_targets)
+            key = ("pose", targets is not None, vert)
+            pred = self._dispatch(key, lambda: self._enqueue_pose(*key[1:]))
+            own, own_pred = self._owners(clone)
+            return self._result(pred, own, own_pred, self.same or vert, with_inputs)
+
+    def labels_from_parts(self, parts, verts=False):
+        """Labels for ``set_handles`` from the bounding-box rule: the rule kernel runs once per named part and its ``move_out``
+        becomes label i + 1 for the i-th part (earlier parts win where regions overlap); label ``count`` = len(parts) + 1 =
+        every other handle point of the rule.  Returns ``(labels, count)`` over the cloud (``verts=True``: over the vertices of
+        a separate cloud).  Set-up work, not per drag: len(parts) launches and a few array operations."""
+        import torch
+        from ._lib import on_device
+        parts = list(parts)
+        if not 1 <= len(parts) <= 254 or any(p not in PARTS for p in parts):
+            raise ValueError(f"labels_from_parts: 1..254 names of {PARTS}, got {parts!r}")
+        B, on, cloud_rows, vert_rows = self._layout()
+        rows = vert_rows if verts and not self.same else cloud_rows
+        count = len(parts) + 1
+        with on_device(on):
+            handle = torch.zeros(rows, dtype=torch.uint8, device=on.device)      # (zeros: padding rows, which no kernel writes, are free points)
+            move = torch.zeros(rows, dtype=torch.uint8, device=on.device)
+            labels = None
+            for i in reversed(range(len(parts))):
+                words = pack_params(B, parts[i], (0.0, 0.0, 0.0), self.partial_range, self.cliptail)
+                self.params.copy_(torch.from_numpy(words), non_blocking=True)
+                self._rule_flags(verts and not self.same, handle, move)
+                if labels is None:
+                    labels = handle * count
+                labels = torch.where(move != 0, torch.full_like(labels, i + 1), labels)
+        return labels, count
 
     # ------------------------------------------------------------------ the end
     def _drop_graphs(self):
@@ -310,6 +573,7 @@ class _Session:
 
     def close(self):
         self._drop_graphs()
+        self._forget_handles()
         for name in self._cached:
             setattr(self, name, None)
 
@@ -380,7 +644,6 @@ class EditSession(_Session):
     def _enqueue(self, masks, vert_masks):
         """Everything of a drag that runs on the GPU behind the parameter copy: capturable, reads device tensors only."""
         from . import pointnet2_utils as pu
-        net = self.net
         hm, mm = (self._mask_h, self._mask_m) if masks else (None, None)
         pu.handle_rows(self.surface_rule, self.surface, self.bounds, self.params, self.buf, hm, mm, tgt=self.surface_tgt,
                        handle_out=self.surface_handle)
@@ -388,13 +651,142 @@ class EditSession(_Session):
             vh, vm = (self._vmask_h, self._vmask_m) if masks else (None, None)
             pu.handle_rows(self.verts_rule, self.verts, self.verts_bounds, self.params, self._vrows, vh, vm, tgt=self.verts_tgt,
                            handle_out=self.verts_handle)
-        enc = net.encode(self.buf, geometry=self.geometry)
-        out = {"verts_tgt_pred": net.decode(self.verts2cano, enc)}
+        return self._network(self.buf, self.geometry, self.verts2cano, self.surf2cano, self._surf_idx)
+
+    def _network(self, buf, geometry, verts2cano, surf2cano, surf_idx):
+        """Network 2 over input rows whose columns 3:7 a handle kernel has just written: the encoder over the cached index sets
+        and one decode (two with a separate cloud)."""
+        net = self.net
+        enc = net.encode(buf, geometry=geometry)
+        out = {"verts_tgt_pred": net.decode(verts2cano, enc)}
         if not self.same:
             enc_s = dict(enc)
-            enc_s["query_idx"], enc_s["query_points"] = self._surf_idx, self.surf2cano
-            out["surface_samples_tgt_pred"] = net.decode(self.surf2cano, enc_s)
+            enc_s["query_idx"], enc_s["query_points"] = surf_idx, surf2cano
+            out["surface_samples_tgt_pred"] = net.decode(surf2cano, enc_s)
         return out
+
+    def _enqueue_pose(self, targets, vert):
+        """``_enqueue`` for a pose of the labelled handle set: the labelled kernel in place of the rule's."""
+        from . import pointnet2_utils as pu
+        one = lambda t: t.unsqueeze(0)      # (the kernel's operands carry a leading pose dimension: T = 1 here)
+        mo, tg, vtg = (None, one(self._targets), one(self._vtargets) if vert else None) if targets else (one(self._motions), None, None)
+        pu.handle_set_rows(self.surface, self._labels, one(self.buf), mo, tg, tgt=one(self.surface_tgt), handle_out=self.surface_handle)
+        if vert:
+            pu.handle_set_rows(self.verts, self._vlabels, one(self._vrows), mo, vtg, tgt=one(self.verts_tgt),
+                               handle_out=self.verts_handle)
+        return self._network(self.buf, self.geometry, self.verts2cano, self.surf2cano, self._surf_idx)
+
+    def _rule_flags(self, verts, handle_out, move_out):
+        """The rule kernel once on ``self.params`` as they stand, for its flags alone (labels_from_parts)."""
+        import torch
+        from . import pointnet2_utils as pu
+        rule, src, bounds = (self.verts_rule, self.verts, self.verts_bounds) if verts else (self.surface_rule, self.surface, self.bounds)
+        rows = torch.empty(tuple(src.shape[:2]) + (7,), dtype=torch.float32, device=src.device)      # (the kernel's required output)
+        pu.handle_rows(rule, src, bounds, self.params, rows, handle_out=handle_out, move_out=move_out)
+
+    # ------------------------------------------------------------------ T poses per call
+    def _track_state(self, T):
+        """What a track of T poses holds beside the session's own state, made at the first track of this T: the [T * B, S, 7]
+        input rows (pose-major; columns 0:3 written here, once), the canonical coordinates repeated T times, network 2's index
+        sets over those T * B rows -- searched once here on the repeated coordinates, which gives every copy its shape's sets --
+        and the buffers of the targets.  Network 1 is not run: its outputs are the session's."""
+        import torch
+        from types import SimpleNamespace
+        if T not in self._tracks:
+            B, S, V = self.surface.shape[0], self.surface.shape[1], self.verts.shape[1]
+            dev = self.verts.device
+            st = SimpleNamespace(targets=None, vtargets=None)
+            st.surf2cano = self.surf2cano.repeat(T, 1, 1).contiguous()
+            st.verts2cano = st.surf2cano if self.same else self.verts2cano.repeat(T, 1, 1).contiguous()
+            st.buf = torch.zeros((T * B, S, 7), dtype=torch.float32, device=dev)
+            st.buf[:, :, 0:3] = st.surf2cano
+            st.geometry = self.net.geometry(st.verts2cano, st.buf)
+            st.surf_idx = None if self.same else self.net.decoder.geometry(st.surf2cano, st.geometry["encoder"]["anchors"])["query_idx"]
+            st.motions = torch.empty((T, B, self._count, 12), dtype=torch.float32, device=dev)
+            st.surface_tgt = torch.empty((T, B, S, 3), dtype=torch.float32, device=dev)
+            if self.same:
+                st.verts_tgt, st.vrows = st.surface_tgt, None
+            else:
+                st.verts_tgt = torch.empty((T, B, V, 3), dtype=torch.float32, device=dev)
+                st.vrows = torch.empty((T, B, V, 7), dtype=torch.float32, device=dev)      # (the kernel's required output)
+            self._tracks[T] = st
+        return self._tracks[T]
+
+    def _enqueue_track(self, T, targets, vert):
+        from . import pointnet2_utils as pu
+        st = self._tracks[T]
+        B, S = self.surface.shape[0], self.surface.shape[1]
+        mo, tg, vtg = (None, st.targets, st.vtargets if vert else None) if targets else (st.motions, None, None)
+        pu.handle_set_rows(self.surface, self._labels, st.buf.view(T, B, S, 7), mo, tg, tgt=st.surface_tgt, handle_out=self.surface_handle)
+        if vert:
+            pu.handle_set_rows(self.verts, self._vlabels, st.vrows, mo, vtg, tgt=st.verts_tgt, handle_out=self.verts_handle)
+        return self._network(st.buf, st.geometry, st.verts2cano, st.surf2cano, st.surf_idx)
+
+    def track(self, motions=None, targets=None, vert_targets=None, with_inputs=False, clone=True):
+        """T poses of the labelled handle set in one call: ``motions`` [T, B, H, 12] or a list of T ``pack_motions`` inputs, or
+        ``targets`` [T, B, n, 3] on the GPU (``vert_targets`` [T, B, V, 3] for the vertices of a separate cloud).  One launch of
+        the labelled kernel writes the T * B input rows, network 2 runs once over them; a drag of a small mesh is bound by its
+        launches, and here the same launches carry T times the rows.
+
+        Returns ``verts_tgt_pred`` and ``verts_tgt`` [T, B, V, 3], ``surface_samples_tgt_pred`` [T, B, S, 3], the handle masks
+        [B, .] (they do not depend on the pose) and with ``with_inputs`` ``surface_samples_inputs`` [T, B, S, 7].
+
+        A track shares with the session network 1's outputs, the labels and the handle masks; its input rows, its index sets
+        (those of the session's, over T * B rows) and its graphs -- one per (form, T) -- are its own and are made at the first
+        track of a T.  Its predictions are network 2's on T * B rows: the dense layers pick their tiles by row count, so a pose
+        of a track equals the same pose through ``pose`` to rounding, not bit for bit."""
+        import numpy as np
+        import torch
+        from ._lib import on_device
+        vert = self._pose_checks("track", motions, targets, vert_targets)
+        B, S, V, H = self.surface.shape[0], self.surface.shape[1], self.verts.shape[1], self._count
+        if targets is not None:
+            if not torch.is_tensor(targets) or targets.dim() != 4:
+                raise ValueError(f"track: targets must be a float32 GPU tensor [T, {B}, {S}, 3]")
+            T = int(targets.shape[0])
+            self._session_tensor(targets, (T, B, S, 3), torch.float32, "track: targets")
+            if vert:
+                self._session_tensor(vert_targets, (T, B, V, 3), torch.float32, "track: vert_targets")
+        elif isinstance(motions, np.ndarray) or hasattr(motions, "detach"):
+            words = motions.detach().cpu().numpy() if hasattr(motions, "detach") else motions
+            if words.ndim != 4 or tuple(words.shape[1:]) != (B, H, 12):
+                raise ValueError(f"track: an array of motions must be [T, {B}, {H}, 12], got {tuple(words.shape)}")
+            T = int(words.shape[0])
+            words = np.ascontiguousarray(words, dtype=np.float32)
+        else:
+            poses = list(motions)
+            T = len(poses)
+            words = np.stack([pack_motions(B, H, m) for m in poses]) if T else None
+        if T < 1:
+            raise ValueError("track: at least one pose")
+        if T * B > 65535:
+            raise ValueError(self._refused + f"a track of T={T} poses of B={B} shapes: T * B must be at most 65535 (the labelled "
+                             "kernel's grid)")
+        with on_device(self.verts):
+            st = self._track_state(T)
+            if targets is None:
+                st.motions.copy_(torch.from_numpy(words), non_blocking=True)
+            else:
+                for name, value in (("targets", targets), ("vtargets", vert_targets if vert else None)):
+                    if value is not None:
+                        if getattr(st, name) is None:
+                            setattr(st, name, torch.empty_like(value, memory_format=torch.contiguous_format))
+                        getattr(st, name).copy_(value, non_blocking=True)
+            key = ("track", T, targets is not None, vert)
+            pred = self._dispatch(key, lambda: self._enqueue_track(*key[1:]))
+            own, own_pred = self._owners(clone)
+            have_verts = self.same or vert
+            out = {"verts_tgt_pred": own_pred(pred["verts_tgt_pred"]).view(T, B, V, 3)}
+            out["surface_samples_tgt_pred"] = (out["verts_tgt_pred"] if self.same
+                                               else own_pred(pred["surface_samples_tgt_pred"]).view(T, B, S, 3))
+            out["verts_tgt"] = own(st.verts_tgt) if have_verts else None
+            out["cano_handle_vert_idx"] = own(self.verts_handle).view(torch.bool) if have_verts else None
+            out["cano_handle_sample_idx"] = (out["cano_handle_vert_idx"] if self.same
+                                             else own(self.surface_handle).view(torch.bool))
+            if with_inputs:
+                out["surface_samples_inputs"] = torch.cat([self.surface.unsqueeze(0).expand(T, B, S, 3),
+                                                           st.buf.view(T, B, S, 7)[..., 3:7]], dim=-1)
+            return out
 
     def _result(self, pred, own, own_pred, have_verts, with_inputs):
         """``verts_tgt_pred`` [B, V, 3], ``surface_samples_tgt_pred`` [B, S, 3], ``verts_tgt``, ``cano_handle_vert_idx`` and
@@ -573,7 +965,6 @@ class RaggedEditSession(_Session):
     def _enqueue(self, masks, vert_masks):
         """Everything of a drag that runs on the GPU behind the parameter copy: capturable, reads device tensors only."""
         from . import pointnet2_utils as pu
-        net = self.net
         hm, mm = (self._mask_h, self._mask_m) if masks else (None, None)
         if self.rect:
             pu.handle_rows(self.surface_rule, self.surface, self.bounds, self.params, self.buf, hm, mm, tgt=self.surface_tgt,
@@ -585,6 +976,12 @@ class RaggedEditSession(_Session):
             vh, vm = (self._vmask_h, self._vmask_m) if masks else (None, None)
             pu.handle_rows_ragged(self.verts_rule.packed, self.verts.packed, self.verts.offsets, self.verts_bounds, self.params,
                                   self._vrows, vh, vm, tgt=self.verts_tgt, handle_out=self.verts_handle)
+        return self._network()
+
+    def _network(self):
+        """Network 2 over the input rows a handle kernel has just written: the encoder over the cached index sets and one ragged
+        decode (two with a separate cloud)."""
+        net = self.net
         if self.rect:
             enc = net.encode(self.buf, geometry=self.geometry)
         else:
@@ -596,6 +993,39 @@ class RaggedEditSession(_Session):
             pred = net.decode(self.surf2cano, enc)      # (its query_idx / query_points are the cloud's)
             out["surface_samples_tgt_pred"] = pred if self.rect else pred.packed
         return out
+
+    def _enqueue_pose(self, targets, vert):
+        """``_enqueue`` for a pose of the labelled handle set: the labelled kernels in place of the rule's."""
+        from . import pointnet2_utils as pu
+        mo, tg, vtg = (None, self._targets, self._vtargets if vert else None) if targets else (self._motions, None, None)
+        if self.rect:
+            one = lambda t: None if t is None else t.unsqueeze(0)      # (a leading pose dimension: T = 1)
+            pu.handle_set_rows(self.surface, self._labels, one(self.buf), one(mo), one(tg), tgt=one(self.surface_tgt),
+                               handle_out=self.surface_handle)
+        else:
+            pu.handle_set_rows_ragged(self.surface.packed, self.surface.offsets, self._labels, self.buf, mo, tg,
+                                      tgt=self.surface_tgt, handle_out=self.surface_handle)
+        if vert:
+            pu.handle_set_rows_ragged(self.verts.packed, self.verts.offsets, self._vlabels, self._vrows, mo, vtg,
+                                      tgt=self.verts_tgt, handle_out=self.verts_handle)
+        return self._network()
+
+    def _rule_flags(self, verts, handle_out, move_out):
+        """The rule kernel once on ``self.params`` as they stand, for its flags alone (labels_from_parts)."""
+        import torch
+        from . import pointnet2_utils as pu
+        if not verts and self.rect:
+            rows = torch.empty(tuple(self.surface.shape[:2]) + (7,), dtype=torch.float32, device=self.surface.device)
+            pu.handle_rows(self.surface_rule, self.surface, self.bounds, self.params, rows, handle_out=handle_out, move_out=move_out)
+            return
+        rule, src, bounds = (self.verts_rule, self.verts, self.verts_bounds) if verts else (self.surface_rule, self.surface, self.bounds)
+        rows = torch.empty((src.capacity, 7), dtype=torch.float32, device=src.device)      # (the kernel's required output)
+        pu.handle_rows_ragged(rule.packed, src.packed, src.offsets, bounds, self.params, rows, handle_out=handle_out, move_out=move_out)
+
+    def track(self, *args, **kwargs):
+        raise ValueError(self._refused + "a track over a packed session: the packed index sets name packed rows -- T poses would "
+                         "need them rebuilt over T copies of the packed layout, which is not done here; call pose() per pose, or "
+                         "track() on an EditSession per mesh")
 
     def _result(self, pred, own, own_pred, have_verts, with_inputs):
         """``verts_tgt_pred``, ``verts_tgt`` and ``cano_handle_vert_idx`` as RaggedPoints over the vertices' offsets (the handle
@@ -663,6 +1093,52 @@ def reference_data_dict(verts_src, surface, spec_or_params, cano=None, surface_c
             "cano_handle_vert_idx": vh, "cano_handle_sample_idx": sh}
 
 
+def reference_pose_dict(verts_src, surface, labels, count, motions=None, targets=None, vert_labels=None, vert_targets=None):
+    """The data_dict one pose of a labelled handle set stands for, built with torch alone, what ``pose`` and the labelled kernels
+    are compared with: per coordinate ((M0 * x + M1 * y) + M2 * z) + M3 as SEPARATE multiplications and additions in the order of
+    include/nsdp_handle_sets.h (no addcmul, no matmul: each would round elsewhere), free points copied.  ``labels`` [B, n] uint8
+    over the cloud (``surface``, or the vertices when it is None), ``vert_labels`` [B, V] for the vertices of a separate cloud
+    (without them ``verts_tgt`` and ``cano_handle_vert_idx`` are None); ``motions``: anything ``pack_motions`` takes, or
+    ``targets`` [B, n, 3] (``vert_targets`` [B, V, 3])."""
+    import torch
+    if (motions is None) == (targets is None):
+        raise ValueError(f"reference_pose_dict: exactly one of motions and targets (got {'neither' if motions is None else 'both'})")
+    B, dev = verts_src.shape[0], verts_src.device
+    table = None if motions is None else torch.from_numpy(pack_motions(B, count, motions)).to(dev)
+
+    def one(src, lab, tgt_given):
+        if table is None:
+            handle = lab != 0
+            moved = tgt_given
+        else:
+            handle = (lab >= 1) & (lab <= count)
+            pick = (lab.long() - 1).clamp(0, count - 1)                                  # (a free point's pick is not used)
+            M = torch.gather(table, 1, pick[:, :, None].expand(B, lab.shape[1], 12))      # [B, n, 12]: a copy of the rows
+            x, y, z = src[:, :, 0], src[:, :, 1], src[:, :, 2]
+            cols = []
+            for c in range(3):
+                acc = M[:, :, 4 * c] * x
+                acc = acc + M[:, :, 4 * c + 1] * y
+                acc = acc + M[:, :, 4 * c + 2] * z
+                cols.append(acc + M[:, :, 4 * c + 3])
+            moved = torch.stack(cols, dim=-1)
+        return handle, torch.where(handle[:, :, None], moved, src)
+
+    same = surface is None
+    surf = verts_src if same else surface
+    sh, st = one(surf, labels, targets)
+    if same:
+        vh, vt = sh, st
+    elif vert_labels is not None and (targets is None or vert_targets is not None):
+        vh, vt = one(verts_src, vert_labels, vert_targets)
+    else:
+        vh = vt = None
+    maskf = sh[:, :, None].float()
+    return {"surface_samples_inputs": torch.cat([surf, st * maskf, maskf], dim=-1).contiguous(),
+            "surface_samples_src": surf.contiguous(), "verts_src": verts_src.contiguous(), "verts_tgt": vt,
+            "cano_handle_vert_idx": vh, "cano_handle_sample_idx": sh}
+
+
 # ---------------------------------------------------------------------------------------------------------------- the tool
 def build_parser():
     ap = argparse.ArgumentParser(description="Drag handles on a (synthetic) mesh through an editing session, timed")
@@ -680,6 +1156,13 @@ def build_parser():
     ap.add_argument("--part", default=None, choices=PARTS, help="the region that moves (default: the config's data.userhandle)")
     ap.add_argument("--translate", default=None, metavar="dx,dy,dz",
                     help="its translation (default: the config's xtrans, ytrans, ztrans)")
+    ap.add_argument("--handles", default=None, metavar="p1,p2,...",
+                    help="a labelled handle set from these parts of the rule (labels_from_parts): the first takes --rotate-deg "
+                         "about its own centroid plus --translate, the others are pinned, through pose() -- or track() with --track")
+    ap.add_argument("--rotate-deg", type=float, default=0.0, help="with --handles: the first handle's rotation in degrees")
+    ap.add_argument("--axis", default="0,0,1", metavar="ax,ay,az", help="with --handles: the rotation's axis (default 0,0,1)")
+    ap.add_argument("--track", type=int, default=None, metavar="T",
+                    help="with --handles: T poses per call, pose i the motion scaled by (i + 1) / T")
     ap.add_argument("--drags", type=int, default=10, help="timed drags (each with another translation)")
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--graph", action="store_true", help="capture the drag once and replay it")
@@ -842,9 +1325,101 @@ def main_ragged(args, vertex_counts, surface_counts):
     return 0
 
 
+def handles_from_args(args):
+    """(--handles as a list of part names, --axis as three floats); (None, None) without --handles."""
+    if args.handles is None:
+        if args.track is not None or args.rotate_deg:
+            sys.exit("nsdp_amd.edit: --track and --rotate-deg go with --handles")
+        return None, None
+    names = [p for p in args.handles.split(",") if p]
+    if not names or any(p not in PARTS for p in names) or len(set(names)) != len(names):
+        sys.exit(f"nsdp_amd.edit: --handles wants distinct names of {PARTS}, got {args.handles!r}")
+    try:
+        axis = tuple(float(v) for v in args.axis.split(","))
+    except ValueError:
+        axis = ()
+    if len(axis) != 3 or not any(axis):
+        sys.exit(f"nsdp_amd.edit: --axis wants a non-zero ax,ay,az, got {args.axis!r}")
+    if args.track is not None and args.track < 1:
+        sys.exit("nsdp_amd.edit: --track wants a positive integer")
+    return names, axis
+
+
+def main_handles(args, names, axis):
+    """--handles: a labelled handle set from the rule's parts, the first handle rotated about its own centroid and translated,
+    the others pinned -- one pose per call, or with --track T poses per call (pose i: the motion scaled by (i + 1) / T)."""
+    device, config, spec, model, test_fn, timed, translation = _setup(args, args.surface or args.vertices)
+    import numpy as np
+    import torch
+    from . import pointnet2_utils, synth
+    from .infer import _checksum
+    from .model.deformation_networks import test_on_batch_with_cano
+    batch = args.batch or int((config.get("test") or {}).get("batch_size", 1) or 1)
+    verts = torch.from_numpy(synth.uniform(SEED_DATA, "mesh_verts", (batch, args.vertices, 3), -0.5, 0.5)).to(device)
+    surface = None if args.surface is None else \
+        torch.from_numpy(synth.uniform(SEED_DATA, "mesh_surface", (batch, args.surface, 3), -0.5, 0.5)).to(device)
+    T = args.track
+    with torch.no_grad():
+        session = EditSession(model, verts, surface, partial_range=spec.partial_range, cliptail=spec.cliptail, graph=args.graph)
+        labels, count = session.labels_from_parts(names)
+        session.set_handles(labels, count, None if surface is None else session.labels_from_parts(names, verts=True)[0])
+        cloud = verts if surface is None else surface
+        first = (labels == 1)[:, :, None].double()
+        pivots = ((cloud.double() * first).sum(dim=1) / first.sum(dim=1).clamp(min=1.0)).cpu().numpy()      # [B, 3], set-up
+
+        def motions(scale, i=0):
+            d = np.asarray(translation(i), dtype=np.float64) * scale
+            return [[Motion.rotate(axis, args.rotate_deg * scale, pivot=pivots[b]).then(Motion.translate(d))]
+                    + [Motion.identity()] * (count - 1) for b in range(batch)]
+
+        def call(i, **kw):
+            if T is None:
+                return session.pose(motions(1.0, i), **kw)
+            return session.track([motions((t + 1) / T, i) for t in range(T)], **kw)
+
+        for i in range(max(args.warmup, 1)):      # (--graph: the first call captures)
+            call(i)
+        out = {}
+        ms_call = timed(lambda i: out.update(call(i, clone=False)), args.drags)
+        out = call(args.drags - 1, with_inputs=True)
+        inputs = out["surface_samples_inputs"]
+        if T is None:
+            dd = {"surface_samples_inputs": inputs, "verts_src": verts, "surface_samples_src": inputs[:, :, 0:3].contiguous()}
+            full = test_fn(model, dd, config)[1]
+        else:      # a track is network 2 over T * B rows: its own step function on those rows and network 1's cached outputs
+            rows = torch.cat([session.surf2cano.repeat(T, 1, 1), inputs[..., 3:7].reshape(T * batch, -1, 4)], dim=-1).contiguous()
+            dd = {"surface_samples_inputs": rows, "surface_samples_src": rows[:, :, 0:3].contiguous(),
+                  "verts_src": session.verts2cano.repeat(T, 1, 1).contiguous()}
+            full = test_on_batch_with_cano(session.net, dd, config)[1]
+        equal = all(torch.equal(out[k].reshape(full[k].shape), full[k]) for k in ("verts_tgt_pred", "surface_samples_tgt_pred"))
+        pointnet2_utils.check_fps_cluster()
+    if args.out:
+        os.makedirs(args.out, exist_ok=True)
+        for k in ("verts_tgt_pred", "surface_samples_tgt_pred", "verts_tgt"):
+            np.save(os.path.join(args.out, k + ".npy"), out[k].cpu().numpy())
+    poses = T or 1
+    line = {"metric": "edit_session_handle_sets", "model_type": config["model"]["type"], "graph": bool(args.graph), "batch": batch,
+            "vertices": args.vertices, "surface": args.surface, "cloud_is_vertex_set": surface is None, "handles": names,
+            "labels": count, "rotate_deg": args.rotate_deg, "axis": list(axis), "translation": list(spec.translation),
+            "track": T, "partial_range": spec.partial_range, "cliptail": spec.cliptail, "drags": args.drags, "warmup": args.warmup,
+            "handle_points": int(out["cano_handle_sample_idx"].sum()), "ms_per_call": round(ms_call, 4),
+            "ms_per_pose": round(ms_call / poses, 4), "replays": session.replays, "eager_calls": session.eager_calls,
+            "equal_to_full_call": bool(equal), "checksum": _checksum(out["verts_tgt_pred"])}
+    print(json.dumps(line), flush=True)
+    session.close()
+    return 0
+
+
 def main(argv=None):
     args = build_parser().parse_args(list(sys.argv[1:] if argv is None else argv))
     vertex_counts, surface_counts = counts_from_args(args)
+    names, axis = handles_from_args(args)
+    if names is not None:
+        if vertex_counts is not None:
+            sys.exit("nsdp_amd.edit: --handles goes with --vertices / --batch, not with --vertex-counts")
+        if args.vertices < 1 or (args.surface is not None and args.surface < 1) or args.drags < 1:
+            sys.exit("nsdp_amd.edit: --vertices, --surface and --drags want positive integers")
+        return main_handles(args, names, axis)
     if vertex_counts is not None:
         if (args.surface is not None and args.surface < 1) or args.drags < 1:
             sys.exit("nsdp_amd.edit: --surface and --drags want positive integers")

@@ -638,6 +638,96 @@ def handle_rows_ragged(cano, src: torch.Tensor, offsets: torch.Tensor, bounds, p
     return rows
 
 
+# Labelled handle sets (include/nsdp_handle_sets.h, csrc/handle_sets.hip): several handles per shape, each with a 3 x 4 motion of
+# its own, or a target per point; T poses of one source per launch.
+HANDLE_SET_MAX_HANDLES = 255
+HANDLE_SET_MAX_POSE_SHAPES = 65535
+
+
+def _one_of_motions_targets(who, motions, targets):
+    if (motions is None) == (targets is None):
+        raise _lib.NsdpHipError(f"{who}: exactly one of motions and targets (got {'neither' if motions is None else 'both'})")
+    given = motions if targets is None else targets
+    if not torch.is_tensor(given):
+        raise _lib.NsdpHipError(f"{who}: {'motions' if targets is None else 'targets'} must be a torch.Tensor, got "
+                                f"{type(given).__name__}")
+
+
+def handle_set_rows(src: torch.Tensor, labels: torch.Tensor, rows: torch.Tensor, motions=None, targets=None, tgt=None,
+                    handle_out=None) -> torch.Tensor:
+    """T poses of a labelled handle set written into the deformation network's input rows (nsdp_handle_set_rows): src (B,n,3),
+    ``labels`` (B,n) uint8 -- 0 a free point, 1..H a handle, above H a free point -- and exactly one of ``motions`` (T,B,H,12),
+    a row-major [A | t] per (pose, shape, handle), and ``targets`` (T,B,n,3), a target per point (every non-zero label is then a
+    handle).  Columns 3..6 of ``rows`` (T,B,n,7) become [handle * tgt | handle]; columns 0..2 are never written.  ``tgt``
+    (T,B,n,3), ``handle_out`` (B,n) uint8: optional outputs, buffers of the caller's.  T and H are the motion tensor's.  Returns
+    ``rows``."""
+    with on_device(src):
+        _points3("src", src)
+        B, n = int(src.shape[0]), int(src.shape[1])
+        _one_of_motions_targets("handle_set_rows", motions, targets)
+        if motions is not None:
+            if motions.dim() != 4 or motions.shape[1] != B or motions.shape[3] != 12:
+                raise _lib.NsdpHipError(f"handle_set_rows: motions must be (T, {B}, H, 12), got {tuple(motions.shape)}")
+            T, H = int(motions.shape[0]), int(motions.shape[2])
+        else:
+            if targets.dim() != 4 or tuple(targets.shape[1:]) != (B, n, 3):
+                raise _lib.NsdpHipError(f"handle_set_rows: targets must be (T, {B}, {n}, 3), got {tuple(targets.shape)}")
+            T, H = int(targets.shape[0]), 0
+        if not torch.is_tensor(rows) or tuple(rows.shape) != (T, B, n, 7) or (tgt is not None and tuple(tgt.shape) != (T, B, n, 3)):
+            raise _lib.NsdpHipError(f"handle_set_rows: {T} poses of src ({B},{n},3) go with rows ({T},{B},{n},7) and tgt "
+                                    f"({T},{B},{n},3), got rows {tuple(rows.shape) if torch.is_tensor(rows) else type(rows).__name__}"
+                                    + ("" if tgt is None else f", tgt {tuple(tgt.shape)}"))
+        check(lib().nsdp_handle_set_rows(fptr(src, "src"), _labels_ptr(labels, (B, n)),
+                                         optptr(None) if motions is None else fptr(motions, "motions"),
+                                         optptr(None) if targets is None else fptr(targets, "targets"),
+                                         _c_int(B), _c_int(n), _c_int(H), _c_int(T), fptr(rows, "rows"),
+                                         optptr(None) if tgt is None else fptr(tgt, "tgt"),
+                                         _bytes_ptr(handle_out, "handle_out", (B, n)), stream_ptr()), "nsdp_handle_set_rows")
+    return rows
+
+
+def handle_set_rows_ragged(src: torch.Tensor, offsets: torch.Tensor, labels: torch.Tensor, rows: torch.Tensor, motions=None,
+                           targets=None, tgt=None, handle_out=None) -> torch.Tensor:
+    """One pose of a labelled handle set over packed rows (nsdp_handle_set_rows_ragged): src (cap,3), offsets (B+1) int32 on
+    the device, ``labels`` (cap,) uint8 and exactly one of ``motions`` (B,H,12) and ``targets`` (cap,3); columns 3..6 of ``rows``
+    (cap,7) are written for the rows of the B shapes, columns 0..2 and the padding rows never.  ``tgt`` (cap,3), ``handle_out``
+    (cap,): optional outputs.  Returns ``rows``."""
+    with on_device(src):
+        _packed3("src", src)
+        B, cap = _offsets_batch("handle_set_rows_ragged", offsets), int(src.shape[0])
+        _one_of_motions_targets("handle_set_rows_ragged", motions, targets)
+        H = 0
+        if motions is not None:
+            if motions.dim() != 3 or motions.shape[0] != B or motions.shape[2] != 12:
+                raise _lib.NsdpHipError(f"handle_set_rows_ragged: motions must be ({B}, H, 12), got {tuple(motions.shape)}")
+            H = int(motions.shape[1])
+        else:
+            _packed3("targets", targets, cap)
+        if tgt is not None:
+            _packed3("tgt", tgt, cap)
+        if not torch.is_tensor(rows) or tuple(rows.shape) != (cap, 7):
+            raise _lib.NsdpHipError(f"handle_set_rows_ragged: src ({cap},3) goes with rows ({cap},7), got "
+                                    f"{tuple(rows.shape) if torch.is_tensor(rows) else type(rows).__name__}")
+        check(lib().nsdp_handle_set_rows_ragged(fptr(src, "src"), iptr(offsets, "offsets"), _labels_ptr(labels, (cap,)),
+                                                optptr(None) if motions is None else fptr(motions, "motions"),
+                                                optptr(None) if targets is None else fptr(targets, "targets"),
+                                                _c_int(B), _c_int(cap), _c_int(H), fptr(rows, "rows"),
+                                                optptr(None) if tgt is None else fptr(tgt, "tgt"),
+                                                _bytes_ptr(handle_out, "handle_out", (cap,)), stream_ptr()),
+              "nsdp_handle_set_rows_ragged")
+    return rows
+
+
+def _labels_ptr(labels, shape):
+    """The label bytes of a handle set: uint8 only (a bool tensor would name one handle), required."""
+    if not torch.is_tensor(labels) or not labels.is_cuda:
+        raise _lib.NsdpHipError("labels must be a GPU tensor (CPU not supported, no fallback)")
+    if labels.dtype is not torch.uint8 or tuple(labels.shape) != tuple(shape) or not labels.is_contiguous():
+        raise _lib.NsdpHipError(f"labels must be a contiguous uint8 tensor of shape {tuple(shape)}, got {labels.dtype} "
+                                f"{tuple(labels.shape)}")
+    return ctypes.c_void_p(labels.data_ptr())
+
+
 # ------------------------------------------------------------------------------------------------
 # autograd Functions with the reference's names and signatures
 # ------------------------------------------------------------------------------------------------

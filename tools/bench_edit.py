@@ -2,6 +2,7 @@
 
     python tools/bench_edit.py [--sizes 5000,25000,100000] [--reps 5] [--batch 1]
     python tools/bench_edit.py --vertex-counts 25000,9000,40000,12000 [--reps 5]      (profiles/edit_session_ragged.txt)
+    python tools/bench_edit.py --handles 3 --track 4,16 [--sizes ...] [--reps 5]       (profiles/edit_handle_sets.txt)
 
 The tosca user-handle configuration's model (FlowArbitrary, npoints_per_layer [5000, 500, 100]; procedural weights), the cloud
 = the vertex set (the reference's user-handle data set), one mesh of N uniform vertices per size.  Per size one JSON line with the
@@ -30,6 +31,19 @@ the two ways a packed batch could be dragged without it, interleaved in the same
     per_mesh_eager_ms / per_mesh_graph_ms B batch-1 EditSessions, one per mesh, dragged in turn;
     open_ms                               RaggedEditSession.reopen();
     bounds_ms, rows_ms                    nsdp_handle_bounds_ragged and nsdp_handle_rows_ragged alone (windows of 200 launches).
+
+``--handles H [--track T1,T2]``: a labelled handle set of H labels (labels_from_parts of the first H - 1 parts of the rule: the
+first turns about its centroid and moves, the others and the rest of the rule's handle points are pinned), every session with
+``graph=True``, interleaved in the same way:
+
+    set_rows_ms / rule_rows_ms            nsdp_handle_set_rows (T = 1) and nsdp_handle_rows alone on the same rows (windows of 200);
+    pose_graph_ms / drag_graph_ms         EditSession.pose and a rule EditSession.drag, replayed;
+    track_T_ms                            EditSession.track of T poses, replayed: per call and per pose;
+    poses_T_ms / drags_T_ms               the same T poses through T replayed pose calls in turn / the parent's way of getting T
+                                          poses: T replayed rule drags; per T calls and per pose;
+    first_track_T_ms                      the first track of a T, once: its index sets over T * B rows, its buffers and the capture
+                                          (host clock around the call and a synchronize);
+    equal                                 a pose's predictions are bit-equal to the full call's on reference_pose_dict's data_dict.
 """
 import argparse
 import json
@@ -43,7 +57,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from nsdp_amd import pointnet2_utils as pu, synth                                  # noqa: E402
 from nsdp_amd.config import default_config                                         # noqa: E402
-from nsdp_amd.edit import EditSession, HandleSpec, RaggedEditSession, pack_params, reference_data_dict  # noqa: E402
+from nsdp_amd.edit import (PARTS, EditSession, HandleSpec, Motion, RaggedEditSession, pack_motions, pack_params,  # noqa: E402
+                           reference_data_dict, reference_pose_dict)
 from nsdp_amd.model import build_model                                             # noqa: E402
 from nsdp_amd.model.flow_arbitrary import test_on_batch_with_arbitrary             # noqa: E402
 from nsdp_amd.query_shard import QueryShards, query_sharded                        # noqa: E402
@@ -201,12 +216,88 @@ def bench_ragged(model, counts, reps, dev):
     return line
 
 
+def bench_handles(model, N, batch, reps, dev, H, tracks):
+    import time
+    verts = torch.from_numpy(synth.uniform(1000, "mesh_verts", (batch, N, 3), -0.5, 0.5)).to(dev)
+    calls = 20 if N <= 25000 else 10
+
+    def translation(i):
+        return tuple(v * (1.0 + 0.01 * (i % 7)) for v in SPEC.translation)
+
+    dragged, posed = EditSession(model, verts, graph=True), EditSession(model, verts, graph=True)
+    labels, count = posed.labels_from_parts(PARTS[:H - 1])
+    posed.set_handles(labels, count)
+    first = (labels == 1)[:, :, None].double()
+    pivots = ((verts.double() * first).sum(dim=1) / first.sum(dim=1).clamp(min=1.0)).cpu().numpy()
+
+    def motions(i, scale=1.0):
+        return [[Motion.rotate((0, 0, 1), (10.0 + i % 7) * scale, pivot=pivots[b]).then(
+            Motion.translate([v * scale for v in translation(i)]))] + [Motion.identity()] * (count - 1) for b in range(batch)]
+
+    def track_of(i, T):
+        return [motions(i, (t + 1) / T) for t in range(T)]
+
+    out = posed.pose(motions(3), with_inputs=True)
+    dd = reference_pose_dict(verts, None, labels, count, motions=motions(3))
+    want = test_on_batch_with_arbitrary(model, {k: dd[k] for k in ("surface_samples_inputs", "surface_samples_src", "verts_src")}, None)[1]
+    equal = torch.equal(out["surface_samples_inputs"], dd["surface_samples_inputs"]) and all(torch.equal(out[k], want[k]) for k in KEYS)
+    first_track = {}
+    for T in tracks:      # the one-off cost of a T, on the host's clock
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        posed.track(track_of(0, T), clone=False)
+        torch.cuda.synchronize()
+        first_track[f"first_track_{T}_ms"] = round((time.perf_counter() - t0) * 1e3, 3)
+    variants = {"drag_graph_ms": lambda i: dragged.drag(SPEC.part, translation(i), clone=False),
+                "pose_graph_ms": lambda i: posed.pose(motions(i), clone=False)}
+    for T in tracks:
+        variants[f"track_{T}_ms"] = lambda i, T=T: posed.track(track_of(i, T), clone=False)
+        variants[f"poses_{T}_ms"] = lambda i, T=T: [posed.pose(m, clone=False) for m in track_of(i, T)]
+        variants[f"drags_{T}_ms"] = lambda i, T=T: [dragged.drag(SPEC.part, [v * (t + 1) / T for v in translation(i)], clone=False)
+                                                    for t in range(T)]
+    for fn in variants.values():
+        for i in range(3):
+            fn(i)
+    times = {k: [] for k in variants}
+    for _ in range(reps):
+        for k, fn in variants.items():
+            times[k].append(window(fn, calls if k in ("drag_graph_ms", "pose_graph_ms") else max(2, calls // 4)))
+    # the two handle kernels alone, on the same rows
+    params = torch.from_numpy(pack_params(batch, SPEC.part, SPEC.translation, SPEC.partial_range, SPEC.cliptail)).to(dev)
+    table = torch.from_numpy(pack_motions(batch, count, motions(0))).to(dev)[None]
+    rows, tgt = torch.empty(1, batch, N, 7, device=dev), torch.empty(1, batch, N, 3, device=dev)
+    flags = torch.empty(batch, N, dtype=torch.uint8, device=dev)
+    bounds = pu.handle_bounds(verts)
+    kernels = {"rule_rows_ms": lambda i: pu.handle_rows(verts, verts, bounds, params, rows[0], tgt=tgt[0], handle_out=flags),
+               "set_rows_ms": lambda i: pu.handle_set_rows(verts, labels, rows, motions=table, tgt=tgt, handle_out=flags)}
+    for fn in kernels.values():
+        fn(0)
+    for k in kernels:
+        times[k] = []
+    for _ in range(reps):
+        for k, fn in kernels.items():
+            times[k].append(window(fn, KERNEL_WINDOW))
+    pu.check_fps_cluster()
+    line = {"vertices": N, "batch": batch, "labels": count, "tracks": list(tracks), "calls_per_window": calls, "reps": reps,
+            "handle_points": int(out["cano_handle_sample_idx"].sum()), **{k: stats(v) for k, v in times.items()}, **first_track,
+            "equal": bool(equal), "replays": posed.replays, "eager_calls": posed.eager_calls}
+    med = {k: statistics.median(v) for k, v in times.items()}
+    for T in tracks:
+        line[f"per_pose_{T}_ms"] = {k: round(med[f"{k}_{T}_ms"] / T, 4) for k in ("track", "poses", "drags")}
+    for s in (dragged, posed):
+        s.close()
+    return line
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--sizes", default="5000,25000,100000")
     ap.add_argument("--vertex-counts", action="append", default=None, metavar="n1,n2,...",
                     help="a packed batch of meshes of these vertex counts through a RaggedEditSession (may be given several times; "
                          "replaces --sizes and --batch)")
+    ap.add_argument("--handles", type=int, default=None, metavar="H",
+                    help="a labelled handle set of H labels (2..7) through pose() and track() against rule drags")
+    ap.add_argument("--track", default="4,16", metavar="T1,T2", help="with --handles: the track lengths (default 4,16)")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--batch", type=int, default=1)
     args = ap.parse_args(argv)
@@ -224,6 +315,14 @@ def main(argv=None):
         with torch.no_grad():
             for text in args.vertex_counts:
                 print(json.dumps(bench_ragged(model, tuple(int(v) for v in text.split(",")), args.reps, dev)), flush=True)
+        return 0
+    if args.handles is not None:
+        if not 2 <= args.handles <= len(PARTS) + 1:
+            sys.exit(f"tools/bench_edit.py: --handles wants 2..{len(PARTS) + 1} labels (parts of the rule plus the rest of its handle)")
+        tracks = tuple(int(t) for t in args.track.split(",") if t)
+        with torch.no_grad():
+            for N in (int(s) for s in args.sizes.split(",")):
+                print(json.dumps(bench_handles(model, N, args.batch, args.reps, dev, args.handles, tracks)), flush=True)
         return 0
     lines = []
     with torch.no_grad():
