@@ -527,6 +527,7 @@ int launch_nt(const LinearParams &p, hipStream_t st, int grid_y = 1, bool wp = f
   nsdp::prof::Scope scope(nsdp::prof::kLinear, st, 2.0 * p.M * p.N * p.K,
                           4.0 * (static_cast<double>(p.M) * (p.K + p.N) + static_cast<double>(p.N) * p.K));
   const dim3 gr(static_cast<unsigned>(grid), grid_y);
+  NSDP_TRACE("linear_nt<%d,%d,%d>%s y%d", MT, NT, pre, wp ? " wp" : "", grid_y);
   // small-M split-N launch with at most one wave per SIMD: nothing else hides the operand latency -> deep operand
   // ring (with more waves per SIMD its 192 registers cost more occupancy than the ring wins: 16000 rows, 29 -> 40 us)
   if (wp && MT == 1 && NT == 4 && ((p.K + 15) / 16) % 8 == 0 && grid * grid_y * 4 <= 4LL * nsdp::num_cus()) {
@@ -1117,6 +1118,7 @@ static int linear_dispatch(const float *X, const float *W, const float *bias, co
     long long grid = (M + 4LL * slots - 1) / (4LL * slots);
     const long long cap = 8LL * nsdp::num_cus();
     grid = grid < cap ? grid : cap;
+    NSDP_TRACE("linear_k4_fwd%s", wp ? " wp" : "");
     if (wp) hipLaunchKernelGGL((linear_k4_fwd_kernel<true>), dim3(static_cast<unsigned>(grid)), dim3(256), 0, st, p);
     else hipLaunchKernelGGL((linear_k4_fwd_kernel<false>), dim3(static_cast<unsigned>(grid)), dim3(256), 0, st, p);
     return nsdp::launch_status("linear_k4_fwd_kernel");
@@ -1272,6 +1274,7 @@ static int wgrad_f32_impl(const float *dY, const float *X, const float *mask, co
       p.W0 = remask_W;
       p.b0 = remask_bias;
     }
+    NSDP_TRACE("linear_wgrad<%s,%s>", k4 ? (p.W0 ? "k4 remask" : "k4") : pl.vec4 ? "vec4" : "rows", mask ? "mask" : "plain");
     if (k4) {
       if (p.W0) hipLaunchKernelGGL((linear_wgrad_k4_kernel<2>), dim3(gx), dim3(256), 0, st, p);
       else if (mask) hipLaunchKernelGGL((linear_wgrad_k4_kernel<1>), dim3(gx), dim3(256), 0, st, p);

@@ -3,9 +3,14 @@
 //     x = h + m + l,   h = bf16(x), m = bf16(x - h), l = bf16(x - h - m)        (round to nearest, residuals exact)
 //     x * w  ~=  h*wh + h*wm + m*wh + m*wm + h*wl + l*wh                          (6 of the 9 products)
 //
-// The dropped products (m*wl, l*wm, l*wl) are <= 2^-23 |x||w|, the split itself loses <= 2^-24 |x| -- the result
-// is accurate to fp32 rounding level (tests: error vs. an fp64 reference is the same as the exact-fp32 MFMA
-// kernel's), products are exact in the matrix pipe and accumulate in fp32.  v_mfma_f32_16x16x32_bf16 has 16x
+// The dropped products (m*wl, l*wm, l*wl) are <= 2^-23 |x||w|; the split itself loses <= 2^-24 |x| WHERE ALL THREE
+// PLANES ARE NORMAL bf16 NUMBERS, i.e. for |x| >= 2^-102 or so (three planes of 8 bits above 2^-126).  Below that the m
+// and l planes fall into the bf16 subnormals (kept by the VALU split and by the matrix pipe of gfx950: measured,
+// DESIGN 4g) and under them: the split then loses up to 2^-134 absolute, 2^-16 |x| at |x| = 2^-118, where the
+// exact-fp32 kernel loses nothing.  Operands must be finite: an inf plane leaves inf - inf = NaN in the residual.
+// Within the precondition the result is accurate to fp32 rounding level, element by element (tests/dense_ref.py:
+// |error| <= BOUND (u sum |x||w| + ...) against fp64, a bound that a single lost plane product exceeds); products
+// are exact in the matrix pipe and accumulate in fp32.  v_mfma_f32_16x16x32_bf16 has 16x
 // the rate of v_mfma_f32_16x16x4_f32, so 6 products cost 6/16 of the exact path: a 2.67x higher compute
 // roofline (2.5 PF / 6 = 417 TFLOP/s of fp32-equivalent work), which moves the tall-skinny layers of the
 // TDNet path (M ~ 10^6, N, K <= 256) from the MFMA bound to the HBM bound.
