@@ -10,6 +10,7 @@ import torch.nn as nn
 
 from .decoder import decoder_dict
 from .encoder import encoder_dict
+from ..chamfer import training_loss
 from .utils import compute_l2_error
 from .. import ragged
 from ..ragged import RaggedPoints
@@ -147,13 +148,14 @@ class Deformation_Networks(nn.Module):
 
 
 def _loss_with_cano(model, data_dict, config, geometry=None):
-    """forward + l2 loss of train_on_batch_with_cano (reference :66-72), as a tensor.  ``geometry``: model.geometry() of this
-    batch's inputs, computed ahead of the step."""
+    """forward + loss of train_on_batch_with_cano (reference :66-72), as a tensor: the l2 loss, or what
+    ``config["training"]["loss"]`` names (chamfer.training_loss).  ``geometry``: model.geometry() of this batch's inputs,
+    computed ahead of the step."""
     if geometry is not None:
         pred = model(data_dict["space_samples_src"], data_dict["surface_samples_inputs"], geometry=geometry)
     else:
         pred = model(data_dict["space_samples_src"], data_dict["surface_samples_inputs"])
-    return compute_l2_error(pred, data_dict["space_samples_tgt"])
+    return training_loss(config)(pred, data_dict["space_samples_tgt"])
 
 
 def _train_step_with_cano(model, optimizer, data_dict, config, geometry=None):
@@ -177,9 +179,9 @@ train_on_batch_with_cano.loss_fn = _loss_with_cano      # (data-parallel replay:
 
 @torch.no_grad()
 def validate_on_batch_with_cano(model, data_dict, config):
-    """reference model/deformation_networks.py:80-88."""
+    """reference model/deformation_networks.py:80-88; reports the configured loss (chamfer.training_loss)."""
     pred = model(data_dict["space_samples_src"], data_dict["surface_samples_inputs"])
-    return compute_l2_error(pred, data_dict["space_samples_tgt"]).item()
+    return training_loss(config)(pred, data_dict["space_samples_tgt"]).item()
 
 
 def l2_error_of(pred, target):

@@ -9,7 +9,7 @@ import torch.nn as nn
 
 from .. import hip_batchnorm, hip_decoder, precision
 from . import deformation_networks
-from .utils import compute_l2_error
+from ..chamfer import training_loss
 from ..ragged import RaggedPoints
 
 
@@ -87,10 +87,11 @@ def _split(data_dict):
 
 
 def _loss_with_arbitrary(model, data_dict, config):
-    """forward + l2 loss of train_on_batch_with_arbitrary (reference :33-43), as a tensor."""
+    """forward + loss of train_on_batch_with_arbitrary (reference :33-43), as a tensor: the l2 loss, or what
+    ``config["training"]["loss"]`` names (chamfer.training_loss)."""
     src, tgt, mask = _split(data_dict)
     pred = model(data_dict["space_samples_src"], src, tgt, mask)
-    return compute_l2_error(pred, data_dict["space_samples_tgt"])
+    return training_loss(config)(pred, data_dict["space_samples_tgt"])
 
 
 def _train_step_with_arbitrary(model, optimizer, data_dict, config):
@@ -113,10 +114,10 @@ train_on_batch_with_arbitrary.loss_fn = _loss_with_arbitrary
 
 @torch.no_grad()
 def validate_on_batch_with_arbitrary(model, data_dict, config):
-    """reference model/flow_arbitrary.py:51-63."""
+    """reference model/flow_arbitrary.py:51-63; reports the configured loss (chamfer.training_loss)."""
     src, tgt, mask = _split(data_dict)
     pred = model(data_dict["space_samples_src"], src, tgt, mask)
-    return compute_l2_error(pred, data_dict["space_samples_tgt"]).item()
+    return training_loss(config)(pred, data_dict["space_samples_tgt"]).item()
 
 
 @torch.no_grad()

@@ -119,12 +119,22 @@ def _with_next(loader, device):
 
 
 class SyntheticLoader:
-    """``n_batches`` procedural data_dict batches per epoch (same generator as bench.py and the parity fixtures)."""
+    """``n_batches`` procedural data_dict batches per epoch (same generator as bench.py and the parity fixtures).
+    ``uncorresponded = m`` (1 <= m <= n_query): targets without correspondences, for a correspondence-free loss
+    (``training.loss: chamfer``) -- ``space_samples_tgt`` becomes ``[batch, m, 3]``, the first ``m`` rows of a procedural
+    permutation (one per shape) of the corresponded targets: another order and, for m < n_query, another count."""
 
-    def __init__(self, seed, n_batches, batch, n_surf=2048, n_query=8192):
+    def __init__(self, seed, n_batches, batch, n_surf=2048, n_query=8192, uncorresponded=None):
         from . import synth
-        self.batches = [{k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in
-                         synth.make_batch(seed + i, batch, n_surf, n_query).items()} for i in range(n_batches)]
+        if uncorresponded is not None and not 1 <= int(uncorresponded) <= n_query:
+            raise ValueError(f"SyntheticLoader: uncorresponded={uncorresponded} target rows must be in [1, n_query={n_query}]")
+        self.batches = []
+        for i in range(n_batches):
+            data = synth.make_batch(seed + i, batch, n_surf, n_query)
+            if uncorresponded is not None:
+                order = np.argsort(synth.uniform01(seed + i, "uncorresponded", (batch, n_query)), axis=1, kind="stable")
+                data["space_samples_tgt"] = np.take_along_axis(data["space_samples_tgt"], order[:, :int(uncorresponded), None], axis=1)
+            self.batches.append({k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in data.items()})
 
     def __iter__(self):
         return iter(self.batches)
@@ -183,6 +193,9 @@ def main(argv=None):
     ap.add_argument("--batch", type=int, default=8, help="shapes per batch = per GPU and step (the global batch is this x --gpus)")
     ap.add_argument("--surface", type=int, default=2048, help="surface samples per shape of the procedural batches (default 2048)")
     ap.add_argument("--queries", type=int, default=8192, help="query points per shape of the procedural batches (default 8192)")
+    ap.add_argument("--uncorresponded", type=int, default=None, metavar="M",
+                    help="procedural targets without correspondences: M permuted target rows per shape (1 <= M <= --queries); "
+                         "needs a correspondence-free loss (training.loss: chamfer)")
     ap.add_argument("--epochs", type=int, default=None)
     ap.add_argument("--graph", action="store_true",
                     help="capture the train step once and replay it (nsdp_amd.graph_step.GraphedTrainOnBatch): batches of "
@@ -195,6 +208,8 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.surface < 1 or args.queries < 1:
         sys.exit(f"nsdp_amd.train: --surface {args.surface} and --queries {args.queries} must be positive")
+    if args.uncorresponded is not None and not 1 <= args.uncorresponded <= args.queries:
+        sys.exit(f"nsdp_amd.train: --uncorresponded {args.uncorresponded} must be in [1, --queries {args.queries}]")
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if args.gpus is not None and args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return launch_ranks(args.gpus, argv)
@@ -238,9 +253,10 @@ def main(argv=None):
         from .graph_step import GraphedTrainOnBatch
         train_fn = GraphedTrainOnBatch(train_fn, reducer=dp.reducer if dp is not None else None)
     # (one loader of world x synthetic batches: every rank builds the same list and takes its share, DataParallel.shard)
-    train = SyntheticLoader(args.seed, args.synthetic * world, args.batch, n_surf=args.surface, n_query=args.queries)
+    targets = {} if args.uncorresponded is None else {"uncorresponded": args.uncorresponded}
+    train = SyntheticLoader(args.seed, args.synthetic * world, args.batch, n_surf=args.surface, n_query=args.queries, **targets)
     val = SyntheticLoader(args.seed + 10000, max(1, args.synthetic // 4) * world, args.batch, n_surf=args.surface,
-                          n_query=args.queries)
+                          n_query=args.queries, **targets)
     fit(model, (train_fn, val_fn), lr_scheduler, optimizer, train, val, config, args.experiment_directory, args, device,
         log=say, dp=dp)
     if dp is not None:
