@@ -24,6 +24,7 @@ HANDLES_HEADER = os.path.join(os.path.dirname(HERE), "include", "nsdp_handles.h"
 HANDLES_RAGGED_HEADER = os.path.join(os.path.dirname(HERE), "include", "nsdp_handles_ragged.h")
 HANDLE_SETS_HEADER = os.path.join(os.path.dirname(HERE), "include", "nsdp_handle_sets.h")
 CHAMFER_HEADER = os.path.join(os.path.dirname(HERE), "include", "nsdp_chamfer.h")
+JACOBIAN_HEADER = os.path.join(os.path.dirname(HERE), "include", "nsdp_jacobian.h")
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -munsafe-fp-atomics: fp32 atomicAdd lowers to the hardware global_atomic_add_f32 instead of a CAS loop
@@ -64,7 +65,7 @@ def sources():
 
 def _deps_mtime():
     # (this file too: the compiler flags live here)
-    hs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")] + [HEADER, EVAL_HEADER, SAMPLING_HEADER, SEARCH_HEADER, SCATTER_HEADER, HANDLES_HEADER, HANDLES_RAGGED_HEADER, HANDLE_SETS_HEADER, CHAMFER_HEADER, os.path.abspath(__file__)]
+    hs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")] + [HEADER, EVAL_HEADER, SAMPLING_HEADER, SEARCH_HEADER, SCATTER_HEADER, HANDLES_HEADER, HANDLES_RAGGED_HEADER, HANDLE_SETS_HEADER, CHAMFER_HEADER, JACOBIAN_HEADER, os.path.abspath(__file__)]
     return max(os.path.getmtime(h) for h in hs)
 
 

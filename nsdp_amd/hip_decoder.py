@@ -199,6 +199,11 @@ def _shape_tables(pack, z, feats):
 
 def decoder_forward(dec, xyz_q: torch.Tensor, encoding: dict) -> torch.Tensor:
     """xyz_q [B,NQ,3] + encoding {z [B,C], anchors [B,A,3], anchor_feats [B,A,C]} -> [B,NQ,3]."""
+    return _decode(dec, xyz_q, encoding, False)
+
+
+def _decode(dec, xyz_q, encoding, jacobian):
+    """decoder_forward (-> out) and decoder_jacobian (-> (out, jac)): one setup, one search, one table build, one launch."""
     bf16, pack, z, anchors, feats, tables_f32 = _setup(dec, encoding)
     ct = dec.ct1
     B, NQ, _ = xyz_q.shape
@@ -211,13 +216,15 @@ def decoder_forward(dec, xyz_q: torch.Tensor, encoding: dict) -> torch.Tensor:
             idx = pointnet2_utils.knn(xyz_q, anchors, ct.nneigh)                # [B,NQ,k] int32
         qk, vtab, a_g, v_g = _shape_tables(pack, z, feats)
         out = torch.empty(B, NQ, OUT, dtype=torch.float32, device=xyz_q.device)
-        name = "nsdp_decoder_fused_fwd_bf16" if bf16 else "nsdp_decoder_fused_fwd"
+        jac = torch.empty(B, NQ, OUT, 3, dtype=torch.float32, device=xyz_q.device) if jacobian else None
+        name = "nsdp_decoder_jacobian_fwd" if jacobian else "nsdp_decoder_fused_fwd_bf16" if bf16 else "nsdp_decoder_fused_fwd"
         _lib.check(getattr(_lib.lib(), name)(
             _lib.fptr(xyz_q, "xyz_q"), _lib.fptr(anchors, "anchors"), _lib.iptr(idx, "idx"),
             _lib.fptr(qk, "qk"), _lib.fptr(vtab, "vtab"), _lib.fptr(a_g, "a_g"), _lib.fptr(v_g, "v_g"),
-            pack.ptrs, len(pack.tensors), B, NQ, A, ct.nneigh, DIM, HIDDEN, _lib.fptr(out, "out"), _lib.stream_ptr()),
+            pack.ptrs, len(pack.tensors), B, NQ, A, ct.nneigh, DIM, HIDDEN, _lib.fptr(out, "out"),
+            *((_lib.fptr(jac, "jac"),) if jacobian else ()), _lib.stream_ptr()),
             name)
-    return out
+    return (out, jac) if jacobian else out
 
 
 def ragged_refusal(dec):
@@ -245,6 +252,11 @@ def decoder_forward_ragged(dec, points, encoding: dict, out=None):
     why = ragged_refusal(dec)
     if why is not None:
         raise _lib.NsdpHipError("ragged decode refused: " + why)
+    return _decode_ragged(dec, points, encoding, out, False)
+
+
+def _decode_ragged(dec, points, encoding, out, jacobian, jac=None):
+    """decoder_forward_ragged (-> out) and decoder_jacobian_ragged (-> (out, jac)) behind their refusals."""
     bf16, pack, z, anchors, feats, tables_f32 = _setup(dec, encoding)
     ct = dec.ct1
     xyz_q = points.packed.contiguous().float()
@@ -258,6 +270,10 @@ def decoder_forward_ragged(dec, points, encoding: dict, out=None):
             out = torch.empty(cap, OUT, dtype=torch.float32, device=xyz_q.device)
         elif tuple(out.shape) != (cap, OUT):
             raise _lib.NsdpHipError(f"ragged decode: out must be [{cap}, {OUT}], got {tuple(out.shape)}")
+        if jacobian and jac is None:
+            jac = torch.empty(cap, OUT * 3, dtype=torch.float32, device=xyz_q.device)
+        elif jacobian and tuple(jac.shape) != (cap, OUT * 3):
+            raise _lib.NsdpHipError(f"ragged decode: jac must be [{cap}, {OUT * 3}], got {tuple(jac.shape)}")
         if cap:
             idx = encoding.get("query_idx") if encoding.get("query_points") is points else None      # (searched ahead: Deformation_Networks.ragged_geometry)
             if idx is None:
@@ -265,10 +281,49 @@ def decoder_forward_ragged(dec, points, encoding: dict, out=None):
             elif tuple(idx.shape) != (cap, ct.nneigh):
                 raise _lib.NsdpHipError(f"ragged decode: cached query_idx must be [{cap}, {ct.nneigh}], got {tuple(idx.shape)}")
             qk, vtab, a_g, v_g = _shape_tables(pack, z, feats)
-            name = "nsdp_decoder_fused_fwd_bf16_ragged" if bf16 else "nsdp_decoder_fused_fwd_ragged"
+            name = ("nsdp_decoder_jacobian_fwd_ragged" if jacobian else
+                    "nsdp_decoder_fused_fwd_bf16_ragged" if bf16 else "nsdp_decoder_fused_fwd_ragged")
             _lib.check(getattr(_lib.lib(), name)(
                 _lib.fptr(xyz_q, "xyz_q"), _lib.iptr(points.offsets, "offsets"), _lib.fptr(anchors, "anchors"), _lib.iptr(idx, "idx"),
                 _lib.fptr(qk, "qk"), _lib.fptr(vtab, "vtab"), _lib.fptr(a_g, "a_g"), _lib.fptr(v_g, "v_g"),
-                pack.ptrs, len(pack.tensors), B, cap, A, ct.nneigh, DIM, HIDDEN, _lib.fptr(out, "out"), _lib.stream_ptr()),
+                pack.ptrs, len(pack.tensors), B, cap, A, ct.nneigh, DIM, HIDDEN, _lib.fptr(out, "out"),
+                *((_lib.fptr(jac, "jac"),) if jacobian else ()), _lib.stream_ptr()),
                 name)
-    return points.like(out)
+    return (points.like(out), points.like(jac)) if jacobian else points.like(out)
+
+
+def jacobian_refusal(dec):
+    """Why the deformation gradient cannot be computed right now (None: it can).  The Jacobian exists as the fp32 fused kernel
+    alone (include/nsdp_jacobian.h): no layered path, no bf16-operand form, no backward."""
+    if torch.is_grad_enabled():
+        return ("autograd is enabled: the Jacobian is computed by a fused inference kernel in forward mode, which has no "
+                "backward -- call under torch.no_grad()")
+    if not ENABLED:
+        return "the fused decoder is switched off (NSDP_FUSED_DECODER=0 / hip_decoder.ENABLED = False) and the layered decoder computes no Jacobian"
+    if precision.is_bf16():
+        return "bf16 storage: the Jacobian kernel runs on the fp32 weight pack in fp32 storage only"
+    if MODE == "bf16":
+        return ("bf16 mode (hip_decoder.MODE = 'bf16'): the bf16-operand kernel has no Jacobian form -- select the fp32 kernel "
+                "(NSDP_FUSED_DECODER_DTYPE=f32)")
+    if not supported(dec):
+        return "decoder geometry: the fused kernels are built for dim=200, hidden_dim=128, n_blocks=5, out_dim=3"
+    return None
+
+
+def decoder_jacobian(dec, xyz_q: torch.Tensor, encoding: dict):
+    """``decoder_forward`` together with the deformation gradient: -> (out [B,NQ,3], jac [B,NQ,3,3]), jac[..., i, j] =
+    d out[..., i] / d xyz_q[..., j] with the neighbour indices held fixed (nsdp_decoder_jacobian_fwd).  ``out`` has the bits
+    ``decoder_forward`` gives.  Refused with its reason where it cannot run (jacobian_refusal)."""
+    why = jacobian_refusal(dec)
+    if why is not None:
+        raise _lib.NsdpHipError("decoder Jacobian refused: " + why)
+    return _decode(dec, xyz_q, encoding, True)
+
+
+def decoder_jacobian_ragged(dec, points, encoding: dict, out=None, jac=None):
+    """``decoder_forward_ragged`` together with the deformation gradient: -> (RaggedPoints over [cap,3], RaggedPoints over
+    [cap,9]: row-major 3x3 per row; rows at or beyond offsets[B] are not written; ``out`` / ``jac``: buffers of the caller's)."""
+    why = jacobian_refusal(dec)
+    if why is not None:
+        raise _lib.NsdpHipError("decoder Jacobian refused: " + why)
+    return _decode_ragged(dec, points, encoding, out, True, jac)

@@ -49,6 +49,15 @@ distinct vertices, no degenerate triangle -- and targets = the prediction plus a
 ``metrics_ms_per_mesh_loop`` (eval_metric.compute_evaluation_metrics mesh after mesh, its three read-backs per mesh included;
 both wall-clock, interleaved repetitions, median) and ``metrics_l2_fnc_max_abs_diff`` (batch against loop; ``cd`` uses
 different draws and is not compared).
+
+    python -m nsdp_amd.infer CONFIG [--vertex-counts ...|--batch B --queries NQ] --jacobian
+
+The step with the deformation gradient (``test_on_batch(..., jacobian=True)``: the 3x3 Jacobian of the predicted deformation at
+every mesh vertex, nsdp_amd.deformation_gradient; one GPU, eager, fp32 kernel).  The line carries ``ms_per_call`` of the step
+with the Jacobian beside ``ms_per_call_plain`` of the step without it (interleaved repetitions, median; every repetition in
+``*_reps``), ``equal_to_plain`` (the vertices keep their bits) and per shape ``fold_overs`` (vertices with det J <= 0),
+``det_min`` and ``det_median``.  ``--out DIR`` also writes verts_tgt_jacobian.npy ([B, NQ, 3, 3], or the packed [total, 3, 3]
+rows with verts_offsets.npy under ``--vertex-counts``).  Refused with ``--gpus`` above 1 and with ``--decoder-dtype bf16``.
 """
 from __future__ import annotations
 
@@ -104,6 +113,8 @@ def build_parser():
     ap.add_argument("--metrics", type=int, nargs="?", const=30000, default=None, metavar="P",
                     help="evaluation metrics of the predicted batch in one call, P surface points per mesh (default 30000), "
                          "timed against the per-mesh loop")
+    ap.add_argument("--jacobian", action="store_true",
+                    help="run the step with the deformation gradient at every mesh vertex; fold-overs and det J per shape")
     ap.add_argument("--decoder-dtype", default=None, choices=["f32", "bf16"],
                     help="operand type of the fused decoder kernel on every rank (default: NSDP_FUSED_DECODER_DTYPE, else f32)")
     return ap
@@ -323,6 +334,74 @@ def _ragged_surface(args, config, model, test_fn, dd, scounts, vcounts):
     return 0
 
 
+def _jacobian(args, config, model, test_fn, dd, counts, ns):
+    """The --jacobian run (one GPU, eager): the step with and without the Jacobian, interleaved; fold-overs and det J per shape."""
+    import statistics
+    import numpy as np
+    import torch
+    from . import deformation_gradient, hip_decoder, pointnet2_utils
+    from .ragged import RaggedPoints
+    rdd = {k: v for k, v in dd.items() if k != "verts_tgt"}
+    if counts:
+        rdd["verts_src"] = RaggedPoints.from_list([dd["verts_src"][b, :n] for b, n in enumerate(counts)])
+    B = len(counts) if counts else int(dd["verts_src"].shape[0])
+    nverts = counts or [int(dd["verts_src"].shape[1])] * B
+    plain_dd, jac_dd = dict(rdd), dict(rdd)
+
+    def run_plain():
+        test_fn(model, plain_dd, config)
+
+    def run_jacobian():
+        test_fn(model, jac_dd, config, jacobian=True)
+
+    def timed(fn, n):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        for _ in range(n):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / max(1, n)
+
+    for _ in range(max(1, args.warmup)):
+        run_plain()
+        run_jacobian()
+    reps = {"ms_per_call": [], "ms_per_call_plain": []}
+    for _ in range(max(1, args.reps)):
+        reps["ms_per_call"].append(timed(run_jacobian, args.steps))
+        reps["ms_per_call_plain"].append(timed(run_plain, args.steps))
+    pointnet2_utils.check_fps_cluster()      # (a large surface cloud is sampled by a workgroup cluster: no wait may have given up)
+    raw = lambda t: t.packed if isinstance(t, RaggedPoints) else t
+    J, pred = jac_dd["verts_tgt_jacobian"], jac_dd["verts_tgt_pred"]
+    equal = all(torch.equal(raw(jac_dd[k]), raw(plain_dd[k])) for k in KEYS)
+    det = deformation_gradient.determinant(J)
+    rows = list(torch.split(det[:sum(nverts)], nverts)) if counts else [det[b] for b in range(B)]
+    folds = deformation_gradient.fold_overs(J).tolist()
+    if args.out:
+        os.makedirs(args.out, exist_ok=True)
+        for k in KEYS:
+            np.save(os.path.join(args.out, k + ".npy"), raw(jac_dd[k]).cpu().numpy())
+        if counts:
+            np.save(os.path.join(args.out, "verts_tgt_jacobian.npy"), J.packed[:sum(nverts)].view(-1, 3, 3).cpu().numpy())
+            np.save(os.path.join(args.out, "verts_offsets.npy"), pred.offsets.cpu().numpy())
+        else:
+            np.save(os.path.join(args.out, "verts_tgt_jacobian.npy"), J.cpu().numpy())
+    ms = statistics.median(reps["ms_per_call"])
+    line = {"metric": "dense_inference_jacobian", "model_type": config["model"]["type"], "world": 1, "graph": False,
+            "jacobian": True, "ragged": bool(counts), "vertex_counts": counts or None, "queries": None if counts else nverts[0],
+            "total": sum(nverts), "batch": B, "surface": ns, "steps": args.steps, "warmup": args.warmup, "reps": max(1, args.reps),
+            "decoder_dtype": hip_decoder.MODE,
+            **{k: round(statistics.median(v), 4) for k, v in reps.items()},
+            **{k + "_reps": [round(x, 4) for x in v] for k, v in reps.items()},
+            "query_points_per_s": round(sum(nverts) / (ms / 1e3), 1) if ms > 0 else None,
+            "equal_to_plain": bool(equal), "fold_overs": [int(f) for f in folds],
+            "det_min": [float(r.min()) if r.numel() else None for r in rows],
+            "det_median": [float(r.median()) if r.numel() else None for r in rows]}
+    print(json.dumps(line), flush=True)
+    return 0
+
+
 def _counts_arg(flag, text, positive=False):
     try:
         counts = [int(c) for c in text.split(",") if c.strip() != ""]
@@ -365,6 +444,16 @@ def main(argv=None):
         if scounts and len(scounts) != len(counts):
             sys.exit(f"nsdp_amd.infer: {len(scounts)} surface counts against {len(counts)} vertex counts")
     world = int(os.environ.get("WORLD_SIZE", "1"))
+    if args.jacobian:
+        if args.gpus > 1 or world > 1:
+            sys.exit("nsdp_amd.infer: --jacobian runs on one GPU (query_sharded gathers the predictions alone; splitting the "
+                     "Jacobian over ranks is not implemented)")
+        if args.decoder_dtype == "bf16":
+            sys.exit("nsdp_amd.infer: --jacobian with --decoder-dtype bf16: the bf16-operand decoder kernel has no Jacobian "
+                     "form (the fp32 kernel computes it)")
+        if scounts or args.graph or args.metrics is not None:
+            sys.exit("nsdp_amd.infer: --jacobian runs the eager step over a rectangular surface cloud, alone (not with "
+                     "--surface-counts, --graph or --metrics)")
     if args.metrics is not None and args.metrics < 1:
         sys.exit(f"nsdp_amd.infer: --metrics wants a positive number of surface points, got {args.metrics}")
     if args.metrics is not None and counts and min(counts) < 3:
@@ -420,6 +509,14 @@ def main(argv=None):
     dd["surface_samples_src"] = dd["surface_samples_inputs"][:, :, 0:3].contiguous()
     dd["verts_src"], dd["verts_tgt"] = dd.pop("space_samples_src"), dd.pop("space_samples_tgt")
 
+    if args.jacobian:
+        decoder = getattr(model, "model_deform", model).decoder
+        with torch.no_grad():
+            why = (hip_decoder.jacobian_refusal(decoder) if hasattr(decoder, "ct1") else
+                   f"the {type(decoder).__name__} computes no Jacobian (the cross-attention decoder does)")
+        if why is not None:
+            sys.exit("nsdp_amd.infer: --jacobian: " + why)
+        return _jacobian(args, config, model, test_fn, dd, counts, ns)
     if scounts:
         return _ragged_surface(args, config, model, test_fn, dd, scounts, counts)
     if counts:

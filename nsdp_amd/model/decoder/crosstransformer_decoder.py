@@ -48,7 +48,14 @@ class CrossTransformerDecoder(nn.Module):
         """The index set forward() derives from coordinates alone: each query's nearest anchors."""
         return {"query_idx": ops.knn_indices(xyz_q, anchors, self.ct1.nneigh)}
 
-    def forward(self, xyz_q, encoding):
+    def forward(self, xyz_q, encoding, jacobian=False):
+        """``jacobian=True``: -> (out, jac), jac [B,NQ,3,3] (a RaggedPoints over [cap,9] for packed queries) the deformation
+        gradient d out / d xyz_q with the neighbour indices held fixed; ``out`` keeps its bits.  Inference only, by the fp32
+        fused kernel only: refused with its reason elsewhere (hip_decoder.jacobian_refusal)."""
+        if jacobian:
+            if isinstance(xyz_q, RaggedPoints):
+                return hip_decoder.decoder_jacobian_ragged(self, xyz_q, encoding)
+            return hip_decoder.decoder_jacobian(self, xyz_q, encoding)
         if isinstance(xyz_q, RaggedPoints):
             # the dispatch condition of the fused call below; where that one would fall to the layers this one raises
             # (hip_decoder.ragged_refusal names the reason)

@@ -137,8 +137,15 @@ class Deformation_Networks(nn.Module):
             "decoder geometry: the packed surface samples are decoded by the fused kernels, built for dim=200, hidden_dim=128, "
             "n_blocks=5, out_dim=3")
 
-    def decode(self, points, encoding):
-        """points [B,NQ,3] -> [B,NQ,3]; a RaggedPoints (meshes of different sizes, nsdp_amd.ragged) -> a RaggedPoints."""
+    def decode(self, points, encoding, jacobian=False):
+        """points [B,NQ,3] -> [B,NQ,3]; a RaggedPoints (meshes of different sizes, nsdp_amd.ragged) -> a RaggedPoints.
+        ``jacobian=True``: -> (that, the deformation gradient [B,NQ,3,3] / a RaggedPoints over [cap,9]), cross-attention
+        decoder only (CrossTransformerDecoder.forward)."""
+        if jacobian:
+            if "jacobian" not in inspect.signature(self.decoder.forward).parameters:
+                raise ValueError(f"decode(jacobian=True): the {type(self.decoder).__name__} computes no Jacobian (the cross-attention "
+                                 "decoder does)")
+            return self.decoder(points, encoding, jacobian=True)
         return self.decoder(points, encoding)
 
     def forward(self, points, surface_samples_inputs, geometry=None):
@@ -202,14 +209,21 @@ def check_ragged_surface(inputs, src):
 
 
 @torch.no_grad()
-def test_on_batch_with_cano(model, data_dict, config, compute_loss=False):
+def test_on_batch_with_cano(model, data_dict, config, compute_loss=False, jacobian=False):
     """Dense inference: surface samples, then all mesh vertices (reference :90-109).  ``data_dict["verts_src"]`` may be a
     RaggedPoints (meshes of different vertex counts, packed): ``verts_tgt_pred`` is then one too.  Independently,
     ``surface_samples_inputs`` may be a RaggedPoints of [total, 7] rows (clouds of different sample counts) with
-    ``surface_samples_src`` packed over the same offsets: ``surface_samples_tgt_pred`` then comes back as a RaggedPoints."""
+    ``surface_samples_src`` packed over the same offsets: ``surface_samples_tgt_pred`` then comes back as a RaggedPoints.
+    ``jacobian=True`` also writes ``data_dict["verts_tgt_jacobian"]``, the deformation gradient at every vertex ([B,V,3,3], or a
+    RaggedPoints over [cap,9] for a packed ``verts_src``); ``verts_tgt_pred`` keeps its bits.  Surface samples get none."""
     inputs = data_dict["surface_samples_inputs"]
     check_ragged_surface(inputs, data_dict["surface_samples_src"])
-    if ENCODE_ONCE:
+    if jacobian:
+        # (one encoding whatever ENCODE_ONCE says: the A/B switch of the reference's op sequence has no Jacobian form)
+        encoding = model.encode(inputs)
+        data_dict["surface_samples_tgt_pred"] = model.decode(data_dict["surface_samples_src"], encoding)
+        deformed_verts, data_dict["verts_tgt_jacobian"] = model.decode(data_dict["verts_src"], encoding, jacobian=True)
+    elif ENCODE_ONCE:
         # the reference runs the module twice on the same surface input (:96, :101): same encoding both times
         encoding = model.encode(inputs)
         data_dict["surface_samples_tgt_pred"] = model.decode(data_dict["surface_samples_src"], encoding)

@@ -28,15 +28,26 @@ class FlowArbitrary(nn.Module):
             return precision.storage(torch.float32)
         return contextlib.nullcontext()
 
-    def canonicalize(self, query_sets, surface_samples_src):
+    def canonicalize(self, query_sets, surface_samples_src, jacobian=False):
         """model_canonicalize applied to several query sets against the SAME source cloud: ONE encoder pass, ONE decoder pass
         over the concatenated queries (the decoder has no BatchNorm and treats query points independently).  The reference
         runs the whole network once per set (model/flow_arbitrary.py:19-20); in training mode the two encoder passes see the
         same batch, produce the same tensors and differ only in what they leave in the BatchNorm buffers -- two momentum
         updates from the same batch statistics, num_batches_tracked += 2 -- which hip_batchnorm.running_updates reproduces.
-        Autograd sums the decoder paths into one encoder backward."""
+        Autograd sums the decoder paths into one encoder backward.
+        ``jacobian``: True, or one flag per query set -- a flagged set comes back as (points, deformation gradient) (see
+        Deformation_Networks.decode).  One encoding then and one decode per set: the decoder treats query points independently,
+        so every set gets the bits the concatenated pass gives it."""
         net = self.model_canonicalize
+        flags = [bool(jacobian)] * len(query_sets) if isinstance(jacobian, bool) else [bool(j) for j in jacobian]
+        if len(flags) != len(query_sets):
+            raise ValueError(f"canonicalize(): {len(flags)} jacobian flags for {len(query_sets)} query sets")
         with self._canonicalize_storage(), hip_decoder.canonicalize_mode():
+            if any(flags):
+                with hip_batchnorm.running_updates(len(query_sets)):
+                    encoding = net.encode(surface_samples_src)
+                return [self._decode_canonical(net, q if isinstance(q, RaggedPoints) else q.contiguous(), encoding, jacobian=j)
+                        for q, j in zip(query_sets, flags)]
             if not deformation_networks.ENCODE_ONCE:
                 return [net(q, surface_samples_src) for q in query_sets]
             if any(isinstance(q, RaggedPoints) for q in query_sets):
@@ -55,14 +66,15 @@ class FlowArbitrary(nn.Module):
             return list(torch.split(out, [q.shape[1] for q in query_sets], dim=1))
 
     @staticmethod
-    def _decode_canonical(net, queries, encoding):
+    def _decode_canonical(net, queries, encoding, jacobian=False):
+        kw = {"jacobian": True} if jacobian else {}      # (the plain call stays the call it was: decode(queries, encoding))
         if precision.is_bf16() and precision.canonicalize_decoder_f32():
             # the middle point of the mixed storage (precision.py): bf16 encoder, fp32 decoder -- the encoding (one latent
             # code and 100 anchor features per shape) is cast once, the per-point chain runs in fp32 storage
             with precision.storage(torch.float32):
                 enc32 = {k: (v.float() if torch.is_tensor(v) and v.dtype is torch.bfloat16 else v) for k, v in encoding.items()}
-                return net.decode(queries, enc32)
-        return net.decode(queries, encoding)
+                return net.decode(queries, enc32, **kw)
+        return net.decode(queries, encoding, **kw)
 
     def deform_input(self, surf_src2cano, surface_samples_tgt, cano_handle_sample_mask):
         if isinstance(surf_src2cano, RaggedPoints):      # ragged surface clouds: the packed [capacity, 7] concatenation
@@ -121,13 +133,25 @@ def validate_on_batch_with_arbitrary(model, data_dict, config):
 
 
 @torch.no_grad()
-def test_on_batch_with_arbitrary(model, data_dict, config, compute_loss=False):
+def test_on_batch_with_arbitrary(model, data_dict, config, compute_loss=False, jacobian=False):
     """reference model/flow_arbitrary.py:65-85.  ``data_dict["verts_src"]`` may be a RaggedPoints (meshes of different vertex
     counts, packed): both networks decode it ragged and ``verts_tgt_pred`` is one.  ``surface_samples_inputs`` may be a
     RaggedPoints of [total, 7] rows (clouds of different sample counts): the packed form travels between the two networks and
-    ``surface_samples_tgt_pred`` comes back as a RaggedPoints."""
+    ``surface_samples_tgt_pred`` comes back as a RaggedPoints.
+    ``jacobian=True`` also writes ``data_dict["verts_tgt_jacobian"]`` ([B,V,3,3], or a RaggedPoints over [cap,9] for a packed
+    ``verts_src``): the chain rule J2(q1) @ J1(q) over the two networks (network 2's encoding does not depend on the vertex
+    queries); ``verts_tgt_pred`` keeps its bits.  Surface samples get none."""
     src, tgt, mask = _split(data_dict)
-    if deformation_networks.ENCODE_ONCE:
+    if jacobian:
+        from .. import deformation_gradient
+        surf2cano, (verts2cano, jac1) = model.canonicalize([src, data_dict["verts_src"]], src, jacobian=[False, True])
+        encoding = model.model_deform.encode(model.deform_input(surf2cano, tgt, mask))
+        data_dict["surface_samples_tgt_pred"] = model.model_deform.decode(
+            surf2cano if isinstance(surf2cano, RaggedPoints) else surf2cano.contiguous(), encoding)
+        deformed_verts, jac2 = model.model_deform.decode(
+            verts2cano if isinstance(verts2cano, RaggedPoints) else verts2cano.contiguous(), encoding, jacobian=True)
+        data_dict["verts_tgt_jacobian"] = deformation_gradient.compose(jac2, jac1)
+    elif deformation_networks.ENCODE_ONCE:
         # the reference's two model() calls (:71, :76) run six encoder passes over two distinct clouds: the source cloud
         # (four times) and the canonicalised surface + target + mask (twice).  Two passes here.
         surf2cano, verts2cano = model.canonicalize([src, data_dict["verts_src"]], src)
