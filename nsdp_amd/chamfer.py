@@ -67,16 +67,17 @@ def refusal(pred, target):
     return None
 
 
-def _lists(idx, sources):
+def _lists(idx, sources, who: str = "chamfer_loss"):
     """Ascending inverse lists (offsets [B, sources + 1], entries [B, E]) of idx [B, E] for the backward's fixed summation order.
     ``inverse_lists`` picks the build; where a list could be longer than the one-workgroup build sorts (E > 1024) or the sources
-    exceed its bound, the many-workgroup build is taken by name -- every list it writes is ascending."""
+    exceed its bound, the many-workgroup build is taken by name -- every list it writes is ascending.  ``who``: the loss a refusal
+    names (the local-rigidity loss takes its lists here too)."""
     B, E = int(idx.shape[0]), int(idx.shape[1])
     if E <= SORTED_LIST_MAX and sources <= hip_attention.INVERSE_MAX_SOURCES:
         return hip_attention.inverse_lists(idx, sources)
     if hip_attention.INVERT_WIDE == "0":
         raise NsdpHipError(
-            f"chamfer_loss backward: NSDP_INVERT_WIDE=0 leaves the one-workgroup list build alone, which serves up to "
+            f"{who} backward: NSDP_INVERT_WIDE=0 leaves the one-workgroup list build alone, which serves up to "
             f"{hip_attention.INVERSE_MAX_SOURCES} points and puts lists of up to {SORTED_LIST_MAX} entries in order; {E} entries over "
             f"{sources} points need the many-workgroup build for a fixed summation order")
     with hip_attention.invert_wide_mode("force"):

@@ -11,6 +11,7 @@ import torch.nn as nn
 from .decoder import decoder_dict
 from .encoder import encoder_dict
 from ..chamfer import training_loss
+from ..rigidity import training_regulariser
 from .utils import compute_l2_error
 from .. import ragged
 from ..ragged import RaggedPoints
@@ -156,13 +157,23 @@ class Deformation_Networks(nn.Module):
 
 def _loss_with_cano(model, data_dict, config, geometry=None):
     """forward + loss of train_on_batch_with_cano (reference :66-72), as a tensor: the l2 loss, or what
-    ``config["training"]["loss"]`` names (chamfer.training_loss).  ``geometry``: model.geometry() of this batch's inputs,
-    computed ahead of the step."""
+    ``config["training"]["loss"]`` names (chamfer.training_loss), plus the regulariser of ``config["training"]["rigidity"]``.
+    ``geometry``: model.geometry() of this batch's inputs, computed ahead of the step."""
     if geometry is not None:
         pred = model(data_dict["space_samples_src"], data_dict["surface_samples_inputs"], geometry=geometry)
     else:
         pred = model(data_dict["space_samples_src"], data_dict["surface_samples_inputs"])
-    return training_loss(config)(pred, data_dict["space_samples_tgt"])
+    return _configured_loss(config, pred, data_dict)
+
+
+def _configured_loss(config, pred, data_dict):
+    """The data term ``config["training"]["loss"]`` names and, where ``config["training"]["rigidity"]`` is set, the local-rigidity
+    regulariser of the prediction against ``space_samples_src`` (rigidity.training_regulariser; without the key nothing is added)."""
+    loss = training_loss(config)(pred, data_dict["space_samples_tgt"])
+    reg = training_regulariser(config)
+    if reg is not None:
+        loss = loss + reg(pred, data_dict["space_samples_src"])
+    return loss
 
 
 def _train_step_with_cano(model, optimizer, data_dict, config, geometry=None):
@@ -186,9 +197,10 @@ train_on_batch_with_cano.loss_fn = _loss_with_cano      # (data-parallel replay:
 
 @torch.no_grad()
 def validate_on_batch_with_cano(model, data_dict, config):
-    """reference model/deformation_networks.py:80-88; reports the configured loss (chamfer.training_loss)."""
+    """reference model/deformation_networks.py:80-88; reports the configured loss (chamfer.training_loss) plus the configured
+    regulariser (rigidity.training_regulariser): the sum the train step minimises."""
     pred = model(data_dict["space_samples_src"], data_dict["surface_samples_inputs"])
-    return training_loss(config)(pred, data_dict["space_samples_tgt"]).item()
+    return _configured_loss(config, pred, data_dict).item()
 
 
 def l2_error_of(pred, target):

@@ -9,7 +9,6 @@ import torch.nn as nn
 
 from .. import hip_batchnorm, hip_decoder, precision
 from . import deformation_networks
-from ..chamfer import training_loss
 from ..ragged import RaggedPoints
 
 
@@ -100,10 +99,10 @@ def _split(data_dict):
 
 def _loss_with_arbitrary(model, data_dict, config):
     """forward + loss of train_on_batch_with_arbitrary (reference :33-43), as a tensor: the l2 loss, or what
-    ``config["training"]["loss"]`` names (chamfer.training_loss)."""
+    ``config["training"]["loss"]`` names (chamfer.training_loss), plus the regulariser of ``config["training"]["rigidity"]``."""
     src, tgt, mask = _split(data_dict)
     pred = model(data_dict["space_samples_src"], src, tgt, mask)
-    return training_loss(config)(pred, data_dict["space_samples_tgt"])
+    return deformation_networks._configured_loss(config, pred, data_dict)
 
 
 def _train_step_with_arbitrary(model, optimizer, data_dict, config):
@@ -126,10 +125,10 @@ train_on_batch_with_arbitrary.loss_fn = _loss_with_arbitrary
 
 @torch.no_grad()
 def validate_on_batch_with_arbitrary(model, data_dict, config):
-    """reference model/flow_arbitrary.py:51-63; reports the configured loss (chamfer.training_loss)."""
+    """reference model/flow_arbitrary.py:51-63; reports the configured loss (chamfer.training_loss) plus the configured regulariser."""
     src, tgt, mask = _split(data_dict)
     pred = model(data_dict["space_samples_src"], src, tgt, mask)
-    return training_loss(config)(pred, data_dict["space_samples_tgt"]).item()
+    return deformation_networks._configured_loss(config, pred, data_dict).item()
 
 
 @torch.no_grad()
