@@ -275,3 +275,40 @@ def compute_evaluation_metrics_batch(out_dict, pointcloud_size: int = 30000, gen
     cd = chamfer_distance_batch(sample_points(pred, faces, face_idx, bary).contiguous(),
                                 sample_points(gt, faces, face_idx, bary).contiguous())
     return {"l2": l2, "fnc": fnc, "cd": cd}
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# a prediction against a scan (or a mesh of another topology): no correspondences
+# ------------------------------------------------------------------------------------------------------------------------
+def scan_metrics_batch(verts_pred, faces, scan, pointcloud_size: int = 30000, generator=None, samples=None):
+    """A batch of predicted meshes against scans that share no rows with them: {'p2s', 's2p', 'cd_surface'}, each ``[B]`` fp32
+    on the device, no host synchronisation.  ``p2s``: the per-shape mean (``segment_mean``, sqrt transform) of the EXACT distance
+    from every scan point to the predicted surface (``surface_distance.closest_on_mesh``); ``s2p``: the mean distance from
+    ``pointcloud_size`` samples of the predicted surface (``sample_surface_batch`` / ``sample_points``, or ``samples =
+    (face_idx, bary)``) to their nearest scan point (``nn_dist2``); ``cd_surface``: half their sum.  ``verts_pred`` / ``faces``
+    rectangular or ``RaggedPoints`` as for ``compute_evaluation_metrics_batch``; ``scan`` in the same layout with its own
+    counts ([B, m, 3], or a ``RaggedPoints`` over the same batch)."""
+    from . import surface_distance
+    pred = verts_pred
+    if isinstance(pred, RaggedPoints):
+        pred = pred.like(pred.packed.detach())
+    elif torch.is_tensor(pred):
+        pred = pred.detach()
+    layout = _same_batch("scan_metrics_batch: verts_pred / scan", pred, scan)
+    _mesh_rows("scan_metrics_batch", pred, faces, need_gpu=True)
+    d2, _, _ = surface_distance.closest_on_mesh(scan, pred, faces, return_bary=False)
+    if layout == "ragged":
+        B, dev = pred.batch, pred.device
+        d2, scan_rows, scan_off = d2.packed.reshape(-1).contiguous(), scan.packed.contiguous(), scan.offsets
+    else:
+        B, dev = int(pred.shape[0]), pred.device
+        d2, scan_rows, scan_off = d2.reshape(-1).contiguous(), scan.reshape(-1, 3).contiguous(), _rect_offsets(B, scan.shape[1], dev)
+    p2s = pointnet2_utils.segment_mean(d2, scan_off, sqrt=True)
+    if samples is None:
+        samples = sample_surface_batch(pred, faces, pointcloud_size, generator)
+    face_idx, bary = samples
+    pts = sample_points(pred, faces, face_idx, bary).contiguous()                  # [B, count, 3]
+    count = int(pts.shape[1])
+    back = pointnet2_utils.nn_dist2_ragged(pts.reshape(-1, 3), _rect_offsets(B, count, dev), scan_rows, scan_off)
+    s2p = pointnet2_utils.segment_mean(back, _rect_offsets(B, count, dev), sqrt=True)
+    return {"p2s": p2s, "s2p": s2p, "cd_surface": 0.5 * (p2s + s2p)}

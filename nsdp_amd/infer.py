@@ -48,7 +48,10 @@ distinct vertices, no degenerate triangle -- and targets = the prediction plus a
 ``metrics`` ({'l2', 'fnc', 'cd'}, a list per shape), ``metrics_points``, ``metrics_ms_batch`` (one call and its one read-back),
 ``metrics_ms_per_mesh_loop`` (eval_metric.compute_evaluation_metrics mesh after mesh, its three read-backs per mesh included;
 both wall-clock, interleaved repetitions, median) and ``metrics_l2_fnc_max_abs_diff`` (batch against loop; ``cd`` uses
-different draws and is not compared).
+different draws and is not compared).  ``--scan-points N`` beside it scores every predicted mesh against a synthetic scan of N
+points that shares no rows with it -- drawn on the displaced target surface -- through eval_metric.scan_metrics_batch (the exact
+point-to-surface distance, nsdp_amd.surface_distance): the line gains ``scan_metrics`` ({'p2s', 's2p', 'cd_surface'}, a list
+per shape) and ``scan_points``, and the three figures of every mesh go to stderr.
 
     python -m nsdp_amd.infer CONFIG [--vertex-counts ...|--batch B --queries NQ] --jacobian
 
@@ -113,6 +116,9 @@ def build_parser():
     ap.add_argument("--metrics", type=int, nargs="?", const=30000, default=None, metavar="P",
                     help="evaluation metrics of the predicted batch in one call, P surface points per mesh (default 30000), "
                          "timed against the per-mesh loop")
+    ap.add_argument("--scan-points", type=int, default=None, metavar="N",
+                    help="with --metrics: score every predicted mesh against a synthetic scan of N points that shares no rows "
+                         "with it (exact point-to-surface distance): p2s, s2p and cd_surface per mesh")
     ap.add_argument("--jacobian", action="store_true",
                     help="run the step with the deformation gradient at every mesh vertex; fold-overs and det J per shape")
     ap.add_argument("--decoder-dtype", default=None, choices=["f32", "bf16"],
@@ -181,6 +187,37 @@ def _metrics(args, pred):
             **{k: round(statistics.median(v), 4) for k, v in reps.items()},
             **{k + "_reps": [round(x, 4) for x in v] for k, v in reps.items()},
             "metrics_l2_fnc_max_abs_diff": diff}
+
+
+def _scan_metrics(args, pred):
+    """The --scan-points keys for the predicted vertices (a RaggedPoints or [B, V, 3]): a synthetic scan of N points per shape
+    drawn on the displaced surface of --metrics' target (so no scan point is a row of the prediction), then
+    eval_metric.scan_metrics_batch -- {'p2s', 's2p', 'cd_surface'}, a list per shape."""
+    import torch
+    from . import eval_metric
+    from .ragged import RaggedPoints
+    N, P = int(args.scan_points), int(args.metrics)
+    ragged = isinstance(pred, RaggedPoints)
+    rows = [r.contiguous() for r in pred.split()] if ragged else [pred[b] for b in range(pred.shape[0])]
+    dev = rows[0].device
+    faces = [_synthetic_faces(int(r.shape[0])).to(dev) for r in rows]
+    gen = torch.Generator(device=dev).manual_seed(SEED_DATA + 1)
+    scans = []
+    for r, f in zip(rows, faces):
+        t = r + 0.01 * torch.sin(0.37 * torch.arange(int(r.shape[0]), device=dev, dtype=torch.float32)[:, None]
+                                 + torch.arange(3, device=dev, dtype=torch.float32))
+        face_idx, bary = eval_metric.sample_surface_batch(t[None], f[None], N, gen)
+        scans.append(eval_metric.sample_points(t[None], f[None], face_idx, bary)[0].contiguous())
+    if ragged:
+        m = eval_metric.scan_metrics_batch(RaggedPoints.from_list(rows), RaggedPoints.from_rows(faces), RaggedPoints.from_list(scans),
+                                           pointcloud_size=P, generator=gen)
+    else:
+        m = eval_metric.scan_metrics_batch(torch.stack(rows), torch.stack(faces), torch.stack(scans), pointcloud_size=P, generator=gen)
+    got = {k: v.tolist() for k, v in m.items()}
+    for b in range(len(rows)):
+        print(f"scan metrics, mesh {b} ({int(rows[b].shape[0])} vertices, {N} scan points): p2s {got['p2s'][b]:.6g}  "
+              f"s2p {got['s2p'][b]:.6g}  cd_surface {got['cd_surface'][b]:.6g}", file=sys.stderr)
+    return {"scan_metrics": got, "scan_points": N}
 
 
 def _ragged(args, config, model, test_fn, dd, counts, ns):
@@ -256,6 +293,8 @@ def _ragged(args, config, model, test_fn, dd, counts, ns):
             "equal_to_padded": bool(equal)}
     if args.metrics is not None:
         line.update(_metrics(args, rdd["verts_tgt_pred"].like(pred["verts_tgt_pred"])))
+        if args.scan_points is not None:
+            line.update(_scan_metrics(args, rdd["verts_tgt_pred"].like(pred["verts_tgt_pred"])))
     print(json.dumps(line), flush=True)
     step.close()
     padded.close()
@@ -330,6 +369,8 @@ def _ragged_surface(args, config, model, test_fn, dd, scounts, vcounts):
             "l2_vs_per_shape_loop": l2}
     if args.metrics is not None:
         line.update(_metrics(args, pred))
+        if args.scan_points is not None:
+            line.update(_scan_metrics(args, pred))
     print(json.dumps(line), flush=True)
     return 0
 
@@ -456,6 +497,8 @@ def main(argv=None):
                      "--surface-counts, --graph or --metrics)")
     if args.metrics is not None and args.metrics < 1:
         sys.exit(f"nsdp_amd.infer: --metrics wants a positive number of surface points, got {args.metrics}")
+    if args.scan_points is not None and (args.metrics is None or args.scan_points < 1):
+        sys.exit(f"nsdp_amd.infer: --scan-points wants a positive number of scan points and goes with --metrics, got {args.scan_points}")
     if args.metrics is not None and counts and min(counts) < 3:
         sys.exit("nsdp_amd.infer: --metrics needs at least 3 vertices in every mesh of --vertex-counts")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -580,6 +623,8 @@ def main(argv=None):
                                              "ms_per_call", "replays", "eager_calls")} for r in ranks]}
         if args.metrics is not None:
             line.update(_metrics(args, dd["verts_tgt_pred"]))
+            if args.scan_points is not None:
+                line.update(_scan_metrics(args, dd["verts_tgt_pred"]))
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.destroy_process_group()
