@@ -9,9 +9,9 @@ every nearest neighbour the true correspondent the loss IS the l2 loss, up to ro
 
 Forward: one native call -- the two searches of ``nsdp_nn_dist2`` with indices, the per-shape terms and the scalar reduced in
 double in a fixed order.  Backward: one kernel launch per operand that needs a gradient, a gather-reduce over the inverse lists
-(``hip_attention.inverse_lists``) of the opposite direction's index map, in a fixed order and without floating-point atomics:
-two runs give the same bits, and a captured step replays to the bits of the eager one.  While a stream capture is running the
-list build is a node of the graph (``inverse_lists`` caches nothing then).
+(``hip_attention.ascending_inverse_lists``) of the opposite direction's index map, in a fixed order and without floating-point
+atomics: two runs give the same bits, and a captured step replays to the bits of the eager one.  While a stream capture is
+running the list build is a node of the graph (``inverse_lists`` caches nothing then).
 
 ``training_loss(config)`` is what the step functions call: ``config["training"]["loss"]`` absent or ``"l2"`` ->
 ``compute_l2_error`` itself, ``"chamfer"`` -> this loss with the weights of ``config["training"]["chamfer"]``.
@@ -31,7 +31,6 @@ _ci, _cf = ctypes.c_int, ctypes.c_float
 
 MAX_BATCH = 65535
 MAX_POINTS = 1 << 20            # per shape and cloud: the limit of the searches and of the list build
-SORTED_LIST_MAX = 1024          # nsdp_knn_invert puts lists of up to this many entries in ascending order (kSortMax)
 LOSSES = ("l2", "chamfer")
 
 
@@ -65,23 +64,6 @@ def refusal(pred, target):
     if pred.device != target.device:
         return f"devices: pred on {pred.device}, target on {target.device}"
     return None
-
-
-def _lists(idx, sources, who: str = "chamfer_loss"):
-    """Ascending inverse lists (offsets [B, sources + 1], entries [B, E]) of idx [B, E] for the backward's fixed summation order.
-    ``inverse_lists`` picks the build; where a list could be longer than the one-workgroup build sorts (E > 1024) or the sources
-    exceed its bound, the many-workgroup build is taken by name -- every list it writes is ascending.  ``who``: the loss a refusal
-    names (the local-rigidity loss takes its lists here too)."""
-    B, E = int(idx.shape[0]), int(idx.shape[1])
-    if E <= SORTED_LIST_MAX and sources <= hip_attention.INVERSE_MAX_SOURCES:
-        return hip_attention.inverse_lists(idx, sources)
-    if hip_attention.INVERT_WIDE == "0":
-        raise NsdpHipError(
-            f"{who} backward: NSDP_INVERT_WIDE=0 leaves the one-workgroup list build alone, which serves up to "
-            f"{hip_attention.INVERSE_MAX_SOURCES} points and puts lists of up to {SORTED_LIST_MAX} entries in order; {E} entries over "
-            f"{sources} points need the many-workgroup build for a fixed summation order")
-    with hip_attention.invert_wide_mode("force"):
-        return hip_attention.inverse_lists(idx, sources)
 
 
 def forward_raw(pred, target, w_pt: float = 1.0, w_tp: float = 1.0):
@@ -140,7 +122,7 @@ def backward_operand(x, y, idx_x, idx_y, g, w_direct, w_list):
     B, n_self, n_other = int(x.shape[0]), int(x.shape[1]), int(y.shape[1])
     offsets = entries = None
     if float(_cf(w_list).value) != 0.0:
-        offsets, entries = _lists(idx_y, n_self)
+        offsets, entries = hip_attention.ascending_inverse_lists(idx_y, n_self, who="chamfer_loss")
     grad = torch.empty((B, n_self, 3), dtype=torch.float32, device=x.device)
     null = ctypes.c_void_p(0)
     check(lib().nsdp_chamfer_backward(fptr(x, "self"), fptr(y, "other"), iptr(idx_x, "idx_self"),

@@ -3,49 +3,35 @@
 // backward = one launch per gradient operand, a gather-reduce over the inverse lists of the opposite direction's index map.
 //
 // Backward, MI355X design.  A workgroup owns 256 consecutive rows of one shape; a lane owns a row: its point, its nearest
-// neighbour's difference and its list's bounds.  What sets the cost is the length T of a row's list -- about 1 for two clouds of
-// equal size in general position, every one of the other cloud's rows for collapsed predictions -- so the list sum has three
-// forms, picked per row and all inside the one launch:
-//   * T <= 32: the lane walks its own list (ascending).  The lanes of a wave diverge by at most 32 iterations;
-//   * 32 < T <= 1024: the wave takes the row's list together, lane t entries t, t + 64, ... (each entry index a coalesced read,
-//     each point a 12-byte gather) and a butterfly sums the 64 partial sums -- the ballot of such rows is walked in lane order;
-//   * T > 1024: the workgroup takes it, thread t entries t, t + 256, ..., and a tree in LDS sums the 256 partial sums; the four
-//     waves' ballots of such rows go through LDS, so every thread walks the same rows in the same order (barriers are uniform).
-// Every form's order of additions is a function of the list alone (header: the depth of each), nothing is atomic, and a row's
-// gradient does not depend on what the rows around it hold.  One workgroup per long list is the bound of this design: a list
-// of 100 000 entries is 391 dependent-free gathers per thread, where a lane alone would walk all 100 000.
-#include <cfloat>
-#include <cmath>
-
+// neighbour's difference and its list's bounds.  The list sum is csrc/list_reduce.h's (its three forms, their operation order and
+// depth are documented there); the term of an entry is p - y[entry].
 #include "../../include/nsdp_chamfer.h"
 #include "../../include/nsdp_eval.h"
 #include "common.h"
+#include "list_reduce.h"
 #include "prof.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / 64;
-constexpr int kLaneMax = 32;      // the longest list one lane walks alone
-constexpr int kWaveMax = 1024;    // the longest list one wave shares; longer ones take the workgroup
+using namespace nsdp::lists;      // kThreads, clampi, reduce, tree_sum
+
 constexpr int kMaxBatch = 65535;
 constexpr int kMaxPoints = 1 << 20;
 
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-// sum over entries [lo, hi) in steps of `stride` from lo + first of (p - y[entry]), in that order
-__device__ __forceinline__ void list_sum(const float *__restrict__ y, const int32_t *__restrict__ ent, int n_other, int lo, int hi,
-                                         int first, int stride, float px, float py, float pz, float &sx, float &sy, float &sz) {
-#pragma unroll 4
-  for (int e = lo + first; e < hi; e += stride) {
-    const float *q = y + static_cast<size_t>(clampi(ent[e], 0, n_other - 1)) * 3;
+// the term of a list entry: p - y[entry]
+struct OtherPoint {
+  const float *__restrict__ y;
+  const int32_t *__restrict__ ent;
+  int n_other;
+  __device__ __forceinline__ void add(int slot, float px, float py, float pz, float &sx, float &sy, float &sz) const {
+    const float *q = y + static_cast<size_t>(clampi(ent[slot], 0, n_other - 1)) * 3;
     sx += px - q[0];
     sy += py - q[1];
     sz += pz - q[2];
   }
-}
+};
 
 // grid (ceil(n_self / 256), B).  offsets_all == NULL: no lists (w_list == 0), the list sum is 0.
 __global__ __launch_bounds__(kThreads) void chamfer_backward_kernel(const float *__restrict__ self_all,
@@ -55,16 +41,14 @@ __global__ __launch_bounds__(kThreads) void chamfer_backward_kernel(const float 
                                                                     const int32_t *__restrict__ entries_all,
                                                                     const float *__restrict__ g, int n_self, int n_other,
                                                                     float s_d, float s_l, float *__restrict__ grad_all) {
-  __shared__ float red[3][kThreads];
-  __shared__ unsigned long long big[kWaves];
+  __shared__ Shared shared;
   const size_t b = blockIdx.y;
   const float *x = self_all + b * n_self * 3;
   const float *y = other_all + b * n_other * 3;
   const int32_t *off = offsets_all ? offsets_all + b * (static_cast<size_t>(n_self) + 1) : nullptr;
   const int32_t *ent = offsets_all ? entries_all + b * n_other : nullptr;
-  const int tid = static_cast<int>(threadIdx.x), lane = tid & 63, wave = tid >> 6;
   const int row0 = static_cast<int>(blockIdx.x) * kThreads;
-  const int i = row0 + tid;
+  const int i = row0 + static_cast<int>(threadIdx.x);
   const bool live = i < n_self;
   float px = 0.f, py = 0.f, pz = 0.f, dx = 0.f, dy = 0.f, dz = 0.f;
   int lo = 0, hi = 0;
@@ -78,55 +62,9 @@ __global__ __launch_bounds__(kThreads) void chamfer_backward_kernel(const float 
       hi = clampi(off[i + 1], lo, n_other);
     }
   }
-  const int len = hi - lo;
   float sx = 0.f, sy = 0.f, sz = 0.f;
-  if (off) {      // (uniform over the grid)
-    if (len <= kLaneMax) list_sum(y, ent, n_other, lo, hi, 0, 1, px, py, pz, sx, sy, sz);
-    // rows whose list a wave shares, in lane order (all 64 lanes are here: rows beyond n_self have len 0)
-    unsigned long long todo = __ballot(len > kLaneMax && len <= kWaveMax);
-    while (todo) {
-      const int src = __ffsll(static_cast<long long>(todo)) - 1;
-      todo &= todo - 1;
-      float ax = 0.f, ay = 0.f, az = 0.f;
-      list_sum(y, ent, n_other, __shfl(lo, src), __shfl(hi, src), lane, 64, __shfl(px, src), __shfl(py, src), __shfl(pz, src), ax,
-               ay, az);
-#pragma unroll
-      for (int s = 32; s > 0; s >>= 1) {      // (a + b == b + a: both partners hold the same bits after every level)
-        ax += __shfl_xor(ax, s);
-        ay += __shfl_xor(ay, s);
-        az += __shfl_xor(az, s);
-      }
-      if (lane == src) { sx = ax; sy = ay; sz = az; }
-    }
-    // rows whose list the workgroup shares
-    const unsigned long long mine = __ballot(len > kWaveMax);
-    if (lane == 0) big[wave] = mine;
-    __syncthreads();
-    for (int w = 0; w < kWaves; ++w) {
-      unsigned long long rows = big[w];
-      while (rows) {
-        const int r = w * 64 + __ffsll(static_cast<long long>(rows)) - 1;      // (set only for rows below n_self)
-        rows &= rows - 1;
-        const int ri = row0 + r;
-        const float *p = x + static_cast<size_t>(ri) * 3;
-        const int rlo = clampi(off[ri], 0, n_other), rhi = clampi(off[ri + 1], rlo, n_other);
-        float ax = 0.f, ay = 0.f, az = 0.f;
-        list_sum(y, ent, n_other, rlo, rhi, tid, kThreads, p[0], p[1], p[2], ax, ay, az);
-        red[0][tid] = ax; red[1][tid] = ay; red[2][tid] = az;
-        __syncthreads();
-        for (int s = kThreads / 2; s > 0; s >>= 1) {
-          if (tid < s) {
-            red[0][tid] += red[0][tid + s];
-            red[1][tid] += red[1][tid + s];
-            red[2][tid] += red[2][tid + s];
-          }
-          __syncthreads();
-        }
-        if (tid == r) { sx = red[0][0]; sy = red[1][0]; sz = red[2][0]; }
-        __syncthreads();      // (red is rewritten by the next row)
-      }
-    }
-  }
+  if (off)      // (uniform over the grid: every thread of the workgroup calls it)
+    reduce(OtherPoint{y, ent, n_other}, x, off, n_other, row0, lo, hi, px, py, pz, shared, sx, sy, sz);
   if (live) {
     const float g0 = g[0];
     const float gd = g0 * s_d, gl = g0 * s_l;
@@ -134,15 +72,6 @@ __global__ __launch_bounds__(kThreads) void chamfer_backward_kernel(const float 
     out[0] = gd * dx + gl * sx;
     out[1] = gd * dy + gl * sy;
     out[2] = gd * dz + gl * sz;
-  }
-}
-
-// fixed tree over the 256 partial sums of a workgroup; the result in part[0] (every thread must call it)
-__device__ __forceinline__ void tree_sum(double *part) {
-  __syncthreads();
-  for (int s = kThreads / 2; s > 0; s >>= 1) {
-    if (static_cast<int>(threadIdx.x) < s) part[threadIdx.x] += part[threadIdx.x + s];
-    __syncthreads();
   }
 }
 
@@ -178,8 +107,6 @@ __global__ __launch_bounds__(kThreads) void chamfer_loss_kernel(const double *__
   if (threadIdx.x == 0) loss[0] = static_cast<float>(part[0] / static_cast<double>(B));
 }
 
-bool finite_weight(float w) { return w == w && std::fabs(w) <= FLT_MAX; }
-
 }  // namespace
 
 extern "C" size_t nsdp_chamfer_forward_workspace_bytes(int B) {
@@ -197,7 +124,7 @@ extern "C" int nsdp_chamfer_forward(const float *pred, const float *target, int 
                                     void *workspace, float *dist2_pt, int32_t *idx_pt, float *dist2_tp, int32_t *idx_tp,
                                     float *terms, float *loss, void *stream) {
   CHAMFER_SIZES("chamfer_forward", B, n, m);
-  NSDP_REQUIRE(finite_weight(w_pt) && finite_weight(w_tp), "chamfer_forward: the weights must be finite");
+  NSDP_REQUIRE(nsdp::finite_weight(w_pt) && nsdp::finite_weight(w_tp), "chamfer_forward: the weights must be finite");
   NSDP_REQUIRE(pred && target && workspace && dist2_pt && idx_pt && dist2_tp && idx_tp && terms && loss,
                "chamfer_forward: null pointer");
   NSDP_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, "chamfer_forward: the workspace must be 8-byte aligned");
@@ -216,7 +143,7 @@ extern "C" int nsdp_chamfer_backward(const float *self, const float *other, cons
                                      const int32_t *entries, const float *g, int B, int n_self, int n_other, float w_direct,
                                      float w_list, float *grad, void *stream) {
   CHAMFER_SIZES("chamfer_backward", B, n_self, n_other);
-  NSDP_REQUIRE(finite_weight(w_direct) && finite_weight(w_list), "chamfer_backward: the weights must be finite");
+  NSDP_REQUIRE(nsdp::finite_weight(w_direct) && nsdp::finite_weight(w_list), "chamfer_backward: the weights must be finite");
   NSDP_REQUIRE(self && other && idx_self && g && grad, "chamfer_backward: null pointer");
   const bool lists = w_list != 0.f;
   NSDP_REQUIRE(!lists || (offsets && entries), "chamfer_backward: null pointer (a non-zero list weight needs offsets and entries)");

@@ -4,6 +4,9 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include <cfloat>
+#include <cmath>
+
 #include "../../include/nsdp_hip.h"
 
 namespace nsdp {
@@ -60,5 +63,8 @@ inline int num_cus() {
 }
 
 inline int ceil_div(long long a, long long b) { return static_cast<int>((a + b - 1) / b); }
+
+// a loss weight an entry accepts: neither NaN nor infinite
+inline bool finite_weight(float w) { return w == w && std::fabs(w) <= FLT_MAX; }
 
 }  // namespace nsdp

@@ -22,6 +22,7 @@
 
 #include "../../include/nsdp_eval.h"
 #include "common.h"
+#include "list_reduce.h"
 #include "prof.h"
 #include "ragged.h"
 
@@ -30,6 +31,7 @@
 namespace {
 
 constexpr int kThreads = 256;
+static_assert(kThreads == nsdp::lists::kThreads, "segment_mean_kernel sums its partial sums through the 256-wide tree");
 constexpr int kQ = 4;                      // queries per lane
 constexpr int kQueryTile = kThreads * kQ;  // queries per workgroup (1024)
 constexpr int kTile = 1024;                // source rows per LDS tile (12 KiB in three planes)
@@ -209,11 +211,7 @@ __global__ __launch_bounds__(kThreads) void segment_mean_kernel(const float *__r
     acc += static_cast<double>(transform ? sqrtf(fmaxf(v, 0.f)) : v);
   }
   part[threadIdx.x] = acc;
-  __syncthreads();
-  for (int s = kThreads / 2; s > 0; s >>= 1) {
-    if (static_cast<int>(threadIdx.x) < s) part[threadIdx.x] += part[threadIdx.x + s];
-    __syncthreads();
-  }
+  nsdp::lists::tree_sum(part);
   // (an empty shape: 0 / 0 = NaN, the mean of nothing)
   if (threadIdx.x == 0) out[blockIdx.x] = static_cast<float>(part[0] / static_cast<double>(hi - lo));
 }

@@ -6,36 +6,24 @@
 // gathers; a shape's two clouds are 96 KB each at 8192 points, so they are served from L2) and writes its K residuals side by
 // side.  Backward: a workgroup owns 256 consecutive rows of one shape, a lane a row.  The own-columns sum is K gathers per lane.
 // What sets the cost of the other half is the in-degree T of a row -- about K for a cloud in general position, of the order of m
-// for the lowest-index rows of m duplicates -- so the list sum has the three forms of csrc/chamfer.hip (copied here, not shared:
-// the Chamfer kernels keep their bits), picked per row and all inside the one launch:
-//   * T <= 32: the lane walks its own list (ascending);
-//   * 32 < T <= 1024: the wave takes the row's list together, lane t entries t, t + 64, ..., and a butterfly sums the 64
-//     partial sums -- the ballot of such rows is walked in lane order;
-//   * T > 1024: the workgroup takes it, thread t entries t, t + 256, ..., and a tree in LDS sums the 256 partial sums; the four
-//     waves' ballots of such rows go through LDS, so every thread walks the same rows in the same order (barriers are uniform).
-// Every form's order of additions is a function of the list alone (header: the depth of each) and nothing is atomic.
-#include <cfloat>
-#include <cmath>
-
+// for the lowest-index rows of m duplicates -- so the list sum is csrc/list_reduce.h's, the one the Chamfer backward calls (its
+// three forms, their operation order and depth are documented there); the term of an entry e is r_e (p - x[e div K]).
 #include "../../include/nsdp_rigidity.h"
 #include "common.h"
+#include "list_reduce.h"
 #include "prof.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / 64;
-constexpr int kLaneMax = 32;      // the longest list one lane walks alone
-constexpr int kWaveMax = 1024;    // the longest list one wave shares; longer ones take the workgroup
+using namespace nsdp::lists;      // kThreads, clampi, reduce, tree_sum
+
 constexpr int kMaxBatch = 65535;
 constexpr int kMaxPoints = 1 << 20;
 constexpr int kMaxK = 32;
 constexpr int kMaxEntries = 1 << 25;      // n * K: the bound of the list build
 constexpr int kMaxSlices = 64;            // workgroups that share the sum of a shape's squared residuals
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 // grid (ceil(n / 256), B): resid[b,i,j] = |p_i - p_l|^2 - |s_i - s_l|^2, l = idx[b,i,j]
 __global__ __launch_bounds__(kThreads) void rigidity_resid_kernel(const float *__restrict__ pred_all, const float *__restrict__ src_all,
@@ -56,15 +44,6 @@ __global__ __launch_bounds__(kThreads) void rigidity_resid_kernel(const float *_
     const float cur = nsdp::sq_dist3(px, py, pz, p[l], p[l + 1], p[l + 2]);
     const float rest = nsdp::sq_dist3(qx, qy, qz, s[l], s[l + 1], s[l + 2]);
     out[j] = cur - rest;
-  }
-}
-
-// fixed tree over the 256 partial sums of a workgroup; the result in part[0] (every thread must call it)
-__device__ __forceinline__ void tree_sum(double *part) {
-  __syncthreads();
-  for (int s = kThreads / 2; s > 0; s >>= 1) {
-    if (static_cast<int>(threadIdx.x) < s) part[threadIdx.x] += part[threadIdx.x + s];
-    __syncthreads();
   }
 }
 
@@ -126,20 +105,21 @@ __global__ __launch_bounds__(kThreads) void rigidity_loss_kernel(const double *_
   if (threadIdx.x == 0) loss[0] = static_cast<float>(static_cast<double>(w) * (part[0] / static_cast<double>(B)));
 }
 
-// sum over entries [lo, hi) in steps of `stride` from lo + first of r_e * (p - x[e div K]), in that order
-__device__ __forceinline__ void list_sum(const float *__restrict__ x, const float *__restrict__ r, const int32_t *__restrict__ ent,
-                                         int E, int K, int lo, int hi, int first, int stride, float px, float py, float pz, float &sx,
-                                         float &sy, float &sz) {
-#pragma unroll 4
-  for (int t = lo + first; t < hi; t += stride) {
-    const int e = clampi(ent[t], 0, E - 1);
+// the term of a list entry e: r_e * (p - x[e div K])
+struct WeightedEdge {
+  const float *__restrict__ x;
+  const float *__restrict__ r;
+  const int32_t *__restrict__ ent;
+  int E, K;
+  __device__ __forceinline__ void add(int slot, float px, float py, float pz, float &sx, float &sy, float &sz) const {
+    const int e = clampi(ent[slot], 0, E - 1);
     const float re = r[e];
     const float *q = x + static_cast<size_t>(e / K) * 3;
     sx += re * (px - q[0]);
     sy += re * (py - q[1]);
     sz += re * (pz - q[2]);
   }
-}
+};
 
 // grid (ceil(n / 256), B)
 __global__ __launch_bounds__(kThreads) void rigidity_backward_kernel(const float *__restrict__ pred_all, const int32_t *__restrict__ idx_all,
@@ -147,17 +127,15 @@ __global__ __launch_bounds__(kThreads) void rigidity_backward_kernel(const float
                                                                      const int32_t *__restrict__ offsets_all,
                                                                      const int32_t *__restrict__ entries_all, const float *__restrict__ g,
                                                                      int n, int K, float c, float *__restrict__ grad_all) {
-  __shared__ float red[3][kThreads];
-  __shared__ unsigned long long big[kWaves];
+  __shared__ Shared shared;
   const size_t b = blockIdx.y;
   const int E = n * K;      // (<= 2^25)
   const float *x = pred_all + b * n * 3;
   const float *r = resid_all + b * E;
   const int32_t *off = offsets_all + b * (static_cast<size_t>(n) + 1);
   const int32_t *ent = entries_all + b * E;
-  const int tid = static_cast<int>(threadIdx.x), lane = tid & 63, wave = tid >> 6;
   const int row0 = static_cast<int>(blockIdx.x) * kThreads;
-  const int i = row0 + tid;
+  const int i = row0 + static_cast<int>(threadIdx.x);
   const bool live = i < n;
   float px = 0.f, py = 0.f, pz = 0.f, ox = 0.f, oy = 0.f, oz = 0.f;
   int lo = 0, hi = 0;
@@ -178,52 +156,8 @@ __global__ __launch_bounds__(kThreads) void rigidity_backward_kernel(const float
     lo = clampi(off[i], 0, E);
     hi = clampi(off[i + 1], lo, E);
   }
-  const int len = hi - lo;
-  float sx = 0.f, sy = 0.f, sz = 0.f;
-  if (len <= kLaneMax) list_sum(x, r, ent, E, K, lo, hi, 0, 1, px, py, pz, sx, sy, sz);
-  // rows whose list a wave shares, in lane order (all 64 lanes are here: rows beyond n have len 0)
-  unsigned long long todo = __ballot(len > kLaneMax && len <= kWaveMax);
-  while (todo) {
-    const int src = __ffsll(static_cast<long long>(todo)) - 1;
-    todo &= todo - 1;
-    float ax = 0.f, ay = 0.f, az = 0.f;
-    list_sum(x, r, ent, E, K, __shfl(lo, src), __shfl(hi, src), lane, 64, __shfl(px, src), __shfl(py, src), __shfl(pz, src), ax, ay, az);
-#pragma unroll
-    for (int s = 32; s > 0; s >>= 1) {      // (a + b == b + a: both partners hold the same bits after every level)
-      ax += __shfl_xor(ax, s);
-      ay += __shfl_xor(ay, s);
-      az += __shfl_xor(az, s);
-    }
-    if (lane == src) { sx = ax; sy = ay; sz = az; }
-  }
-  // rows whose list the workgroup shares
-  const unsigned long long mine = __ballot(len > kWaveMax);
-  if (lane == 0) big[wave] = mine;
-  __syncthreads();
-  for (int w = 0; w < kWaves; ++w) {
-    unsigned long long rows = big[w];
-    while (rows) {
-      const int rw = w * 64 + __ffsll(static_cast<long long>(rows)) - 1;      // (set only for rows below n)
-      rows &= rows - 1;
-      const int ri = row0 + rw;
-      const float *p = x + static_cast<size_t>(ri) * 3;
-      const int rlo = clampi(off[ri], 0, E), rhi = clampi(off[ri + 1], rlo, E);
-      float ax = 0.f, ay = 0.f, az = 0.f;
-      list_sum(x, r, ent, E, K, rlo, rhi, tid, kThreads, p[0], p[1], p[2], ax, ay, az);
-      red[0][tid] = ax; red[1][tid] = ay; red[2][tid] = az;
-      __syncthreads();
-      for (int s = kThreads / 2; s > 0; s >>= 1) {
-        if (tid < s) {
-          red[0][tid] += red[0][tid + s];
-          red[1][tid] += red[1][tid + s];
-          red[2][tid] += red[2][tid + s];
-        }
-        __syncthreads();
-      }
-      if (tid == rw) { sx = red[0][0]; sy = red[1][0]; sz = red[2][0]; }
-      __syncthreads();      // (red is rewritten by the next row)
-    }
-  }
+  float sx, sy, sz;
+  reduce(WeightedEdge{x, r, ent, E, K}, x, off, E, row0, lo, hi, px, py, pz, shared, sx, sy, sz);
   if (live) {
     const float gc = g[0] * c;
     float *out = grad_all + (b * n + i) * 3;
@@ -232,8 +166,6 @@ __global__ __launch_bounds__(kThreads) void rigidity_backward_kernel(const float
     out[2] = gc * (oz + sz);
   }
 }
-
-bool finite_weight(float w) { return w == w && std::fabs(w) <= FLT_MAX; }
 
 }  // namespace
 
@@ -253,7 +185,7 @@ extern "C" size_t nsdp_rigidity_forward_workspace_bytes(int B) {
 extern "C" int nsdp_rigidity_forward(const float *pred, const float *source, const int32_t *idx, int B, int n, int K, float w,
                                      void *workspace, float *resid, float *terms, float *loss, void *stream) {
   RIGIDITY_SIZES("rigidity_forward", B, n, K);
-  NSDP_REQUIRE(finite_weight(w), "rigidity_forward: the weight must be finite");
+  NSDP_REQUIRE(nsdp::finite_weight(w), "rigidity_forward: the weight must be finite");
   NSDP_REQUIRE(pred && source && idx && workspace && resid && terms && loss, "rigidity_forward: null pointer");
   NSDP_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, "rigidity_forward: the workspace must be 8-byte aligned");
   hipStream_t st = nsdp::as_stream(stream);
@@ -274,7 +206,7 @@ extern "C" int nsdp_rigidity_forward(const float *pred, const float *source, con
 extern "C" int nsdp_rigidity_backward(const float *pred, const int32_t *idx, const float *resid, const int32_t *offsets,
                                       const int32_t *entries, const float *g, int B, int n, int K, float w, float *grad, void *stream) {
   RIGIDITY_SIZES("rigidity_backward", B, n, K);
-  NSDP_REQUIRE(finite_weight(w), "rigidity_backward: the weight must be finite");
+  NSDP_REQUIRE(nsdp::finite_weight(w), "rigidity_backward: the weight must be finite");
   NSDP_REQUIRE(pred && idx && resid && offsets && entries && g && grad, "rigidity_backward: null pointer");
   const float c = static_cast<float>(static_cast<double>(w) / (static_cast<double>(B) * n * K));
   NSDP_TRACE("rigidity_backward<K=%d>", K);

@@ -7,7 +7,7 @@ import os
 
 import torch
 
-from ._lib import check, fptr, iptr, lib, on_device, optptr, stream_ptr
+from ._lib import NsdpHipError, check, fptr, iptr, lib, on_device, optptr, stream_ptr
 
 _ci = ctypes.c_int
 
@@ -71,6 +71,7 @@ INVERT_WIDE_MIN_SOURCES = 8193
 INVERT_WIDE_MAX_SOURCES, INVERT_WIDE_MAX_ENTRIES = 1 << 20, 1 << 25      # the limits of the entry
 INVERT_WIDE_TILE = 1024             # sources per workgroup of its scan (kScanTile of csrc/invert_wide.hip)
 INVERSE_MAX_SOURCES = 8192          # the bound of the list scatters without the wide build
+SORTED_LIST_MAX = 1024              # nsdp_knn_invert puts lists of up to this many entries in ascending order (kSortMax)
 
 
 def _wide_mode(value, default: str = "1") -> str:
@@ -170,6 +171,23 @@ def inverse_lists(idx, N):
                   "nsdp_knn_invert")
     cache[key] = (offsets, entries)
     return offsets, entries
+
+
+def ascending_inverse_lists(idx, sources, who):
+    """Ascending inverse lists (offsets [B, sources + 1], entries [B, E]) of idx [B, E]: what a loss backward with a fixed
+    summation order reads.  ``inverse_lists`` picks the build; where a list could be longer than the one-workgroup build sorts
+    (E > 1024) or the sources exceed its bound, the many-workgroup build is taken by name -- every list it writes is ascending.
+    ``who``: the loss a refusal names."""
+    E = int(idx.shape[1])
+    if E <= SORTED_LIST_MAX and sources <= INVERSE_MAX_SOURCES:
+        return inverse_lists(idx, sources)
+    if INVERT_WIDE == "0":
+        raise NsdpHipError(
+            f"{who} backward: NSDP_INVERT_WIDE=0 leaves the one-workgroup list build alone, which serves up to "
+            f"{INVERSE_MAX_SOURCES} points and puts lists of up to {SORTED_LIST_MAX} entries in order; {E} entries over "
+            f"{sources} points need the many-workgroup build for a fixed summation order")
+    with invert_wide_mode("force"):
+        return inverse_lists(idx, sources)
 
 
 def segment_sum(src, idx, N, scale=1.0, inv=None, addend=None):

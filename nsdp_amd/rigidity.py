@@ -11,7 +11,7 @@ for; the ``/ 4`` leaves the gradient free of factors.  It needs no second deriva
 
 Forward: one native call -- the residuals, the per-shape terms and the scalar reduced in double in a fixed order.  Backward:
 one kernel launch, the point's own K columns plus a gather-reduce over the ascending inverse lists of ``idx``
-(``hip_attention.inverse_lists`` through ``chamfer._lists``), in a fixed order and without floating-point
+(``hip_attention.ascending_inverse_lists``), in a fixed order and without floating-point
 atomics: two runs give the same bits, and a captured step replays to the bits of the eager one.  While a stream capture is
 running the list build is a node of the graph.
 
@@ -24,7 +24,7 @@ import ctypes
 
 import torch
 
-from . import chamfer
+from . import hip_attention
 from ._lib import NsdpHipError, check, fptr, iptr, lib, on_device, stream_ptr
 from .ragged import RaggedPoints
 
@@ -128,7 +128,7 @@ def backward_raw(pred, idx, resid, g, weight: float = 1.0):
     gradient on the device."""
     B, n, K = int(idx.shape[0]), int(idx.shape[1]), int(idx.shape[2])
     # (ascending lists of idx viewed as [B, n * K]: the many-workgroup build by name beyond 1024 entries or 8192 points per shape)
-    offsets, entries = chamfer._lists(idx.view(B, n * K), n, who="local_rigidity_loss")
+    offsets, entries = hip_attention.ascending_inverse_lists(idx.view(B, n * K), n, who="local_rigidity_loss")
     grad = torch.empty((B, n, 3), dtype=torch.float32, device=pred.device)
     check(lib().nsdp_rigidity_backward(fptr(pred, "pred"), iptr(idx, "idx"), fptr(resid, "resid"), iptr(offsets, "offsets"),
                                        iptr(entries, "entries"), fptr(g, "g"), _ci(B), _ci(n), _ci(K), _cf(weight), fptr(grad),

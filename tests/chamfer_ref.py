@@ -7,13 +7,17 @@
     minimisers in fp64 up to the rounding of an fp32 distance.  It also returns, per element, the sum of the absolute values of
     the terms (what an error envelope scales with) and, per row, the length of its list;
   * ``depth`` / ``envelope_c``: the number of roundings a term of the kernel's gradient goes through, from the operation order
-    documented in include/nsdp_chamfer.h.
+    documented in include/nsdp_chamfer.h (``depth`` and the switches are tests/list_order_ref.py's);
+  * ``ordered``: the gradient rebuilt in fp32 in exactly that order, for index sets that are given -- what the kernel's bits
+    are held to.
 """
+import numpy as np
 import torch
+
+from list_order_ref import LANE_MAX, WAVE_MAX, depth, ordered_sum      # noqa: F401  (re-exported: the tests read them here)
 
 U = 2.0 ** -24                  # unit roundoff of fp32, round to nearest
 DIST_SLACK = 16 * U             # five roundings in ((dx^2 + dy^2) + dz^2) of rounded differences, on either side, and room
-LANE_MAX, WAVE_MAX = 32, 1024   # the list lengths at which the kernel switches its form (include/nsdp_chamfer.h)
 
 
 def dist2_64(P, Q):
@@ -68,13 +72,26 @@ def assert_minimisers(P, Q, idx_pt, idx_tp):
     assert bool((got <= best * (1 + DIST_SLACK)).all()), float(((got - best) / best.clamp_min(1e-300)).max())
 
 
-def depth(lengths):
-    """Additions a term of a list of that length passes through (tensor of lengths -> tensor)."""
-    T = lengths.long()
-    lane = (T - 1).clamp_min(0)
-    wave = (T + 63) // 64 + 5
-    group = (T + 255) // 256 + 7
-    return torch.where(T <= LANE_MAX, lane, torch.where(T <= WAVE_MAX, wave, group))
+def _ordered_operand(X, Y, idx_x, idx_y, w_direct, w_list, g):
+    """d L / d X [B, nx, 3] in fp32, every operation rounded once and in the kernel's order: fl(fl(g s_d) d) + fl(fl(g s_l) S)
+    with s_d = fp32(w_direct / (B nx)) and s_l = fp32(w_list / (B ny)) divided in double, d = x - y[idx_x] and S the ordered
+    sum of x - y_l over the rows l of Y that name x, ascending."""
+    X, Y, idx_x, idx_y = X.numpy(), Y.numpy(), idx_x.long().numpy(), idx_y.long().numpy()
+    B, nx, ny = X.shape[0], X.shape[1], Y.shape[1]
+    gd = np.float32(g) * np.float32(np.float64(np.float32(w_direct)) / (np.float64(B) * nx))
+    gl = np.float32(g) * np.float32(np.float64(np.float32(w_list)) / (np.float64(B) * ny))
+    out = np.empty_like(X)
+    for b in range(B):
+        direct = X[b] - Y[b][idx_x[b]]
+        summed = np.stack([ordered_sum(X[b, i] - Y[b][np.flatnonzero(idx_y[b] == i)]) for i in range(nx)])
+        out[b] = gd * direct + gl * summed
+    assert out.dtype == np.float32
+    return torch.from_numpy(out)
+
+
+def ordered(P, Q, idx_pt, idx_tp, w_pt=1.0, w_tp=1.0, g=1.0):
+    """-> {'dP', 'dQ'}: the gradients [., ., 3] fp32 with the bits the kernel's documented order gives."""
+    return {"dP": _ordered_operand(P, Q, idx_pt, idx_tp, w_pt, w_tp, g), "dQ": _ordered_operand(Q, P, idx_tp, idx_pt, w_tp, w_pt, g)}
 
 
 def envelope_c(lengths):

@@ -8,12 +8,15 @@
     gradient check is about the gather-reduce and nothing else, and no case is ever left out because a residual cancels.  It
     also returns, per element, the sum of the absolute values of the terms and, per row, the length of its list (its in-degree);
   * ``depth`` / ``envelope_c`` and the constants: the roundings a number goes through, from the operation order documented in
-    include/nsdp_rigidity.h.
+    include/nsdp_rigidity.h (``depth`` and the switches are tests/list_order_ref.py's);
+  * ``ordered``: the gradient rebuilt in fp32 in exactly that order, the residuals given -- what the kernel's bits are held to.
 """
+import numpy as np
 import torch
 
+from list_order_ref import LANE_MAX, WAVE_MAX, depth, ordered_sum      # noqa: F401  (re-exported: the tests read them here)
+
 U = 2.0 ** -24                  # unit roundoff of fp32, round to nearest
-LANE_MAX, WAVE_MAX = 32, 1024   # the list lengths at which the kernel switches its form (include/nsdp_rigidity.h)
 # |resid - exact| <= RESID_C * U * (cur + rest): five first-order roundings in ((dx^2 + dy^2) + dz^2) of rounded differences
 # (2 from a rounded difference squared, the product, two additions) on either side and the subtraction's one, 6 in all; 8 leaves
 # the kind of room chamfer_ref.DIST_SLACK leaves (16 over 10) for second-order terms and the yardstick's own rounding.
@@ -78,13 +81,24 @@ def closed_form(P, idx, resid, weight=1.0, g=1.0):
     return c * grad, abs(c) * mass, in_degrees(idx)
 
 
-def depth(lengths):
-    """Additions a term of a list of that length passes through (tensor of lengths -> tensor)."""
-    T = lengths.long()
-    lane = (T - 1).clamp_min(0)
-    wave = (T + 63) // 64 + 5
-    group = (T + 255) // 256 + 7
-    return torch.where(T <= LANE_MAX, lane, torch.where(T <= WAVE_MAX, wave, group))
+def ordered(P, idx, resid, weight=1.0, g=1.0):
+    """d L / d P [B, n, 3] in fp32, every operation rounded once and in the kernel's order: fl(fl(g c) fl(own + S)) with
+    c = fp32(w / (B n K)) divided in double, own the row's K columns r_ij (p_i - p_idx[i,j]) added to 0 in column order and S
+    the ordered sum of r_e (p_i - p_{e div K}) over the entries e that name row i, ascending."""
+    P, idx, r = P.numpy(), idx.long().numpy(), resid.numpy()
+    B, n, K = idx.shape
+    gc = np.float32(g) * np.float32(np.float64(np.float32(weight)) / (np.float64(B) * n * K))
+    out = np.empty_like(P)
+    for b in range(B):
+        own = np.zeros((n, 3), dtype=np.float32)
+        for j in range(K):
+            own = own + r[b, :, j, None] * (P[b] - P[b][idx[b, :, j]])
+        flat, rf = idx[b].reshape(-1), r[b].reshape(-1)
+        lists = [np.flatnonzero(flat == i) for i in range(n)]
+        summed = np.stack([ordered_sum(rf[e, None] * (P[b, i] - P[b][e // K])) for i, e in enumerate(lists)])
+        out[b] = gc * (own + summed)
+    assert out.dtype == np.float32
+    return torch.from_numpy(out)
 
 
 def envelope_c(lengths, K):

@@ -155,7 +155,8 @@ def _designed_lists(lengths, seed, B=2):
 def test_lists_of_every_form_and_at_every_switch(lengths):
     """Empty lists, one entry, and the lengths around the lane / wave (32) and wave / workgroup (1024) switches, in one launch:
     several workgroup-form rows in a workgroup and rows of every form in one wave; then the same forms in a workgroup that is
-    not the first of its shape."""
+    not the first of its shape.  Beyond the envelope, the order of additions is held to the bit: both gradients equal the fp32
+    rebuild of the documented order (chamfer_ref.ordered) on the kernel's own indices."""
     P, Q, owners = _designed_lists(lengths, 5)
     _, _, _, i_pt, _, i_tp = _indices(P, Q)
     assert torch.equal(i_tp.long(), owners)
@@ -164,6 +165,10 @@ def test_lists_of_every_form_and_at_every_switch(lengths):
     first = _run(P, Q)
     assert torch.equal(chamfer_ref.closed_form(P, Q, i_pt, i_tp)["dP"][2][0], torch.tensor(lengths))
     _check_gradients(P, Q, first, i_pt, i_tp)
+    want = chamfer_ref.ordered(P, Q, i_pt, i_tp)
+    for name in ("dP", "dQ"):
+        print(f"{name}: {int((first[name] != want[name]).sum())} elements differ from the documented order's bits")
+        assert torch.equal(first[name], want[name]), name
     again = _run(P, Q)
     for key in first:
         assert torch.equal(first[key], again[key]), key

@@ -96,7 +96,8 @@ def _designed_indices(degrees, K, seed, B=2):
 def test_lists_of_every_form_and_at_every_switch(K):
     """Empty lists, one entry, and the in-degrees around the lane / wave (32) and wave / workgroup (1024) switches, in one
     launch: rows of every form in one wave, several workgroup-form rows in a workgroup.  K = 4 exercises e div K.  Two runs give
-    the same bits."""
+    the same bits.  Beyond the envelope, the order of additions is held to the bit: the gradient equals the fp32 rebuild of the
+    documented order (rigidity_ref.ordered) on the kernel's own residuals."""
     idx = _designed_indices(DEGREES, K, 5 + K)
     B, n = idx.shape[0], idx.shape[1]
     assert n == sum(DEGREES) // K
@@ -104,6 +105,9 @@ def test_lists_of_every_form_and_at_every_switch(K):
     first = _run(P, S, idx)
     lengths = _check(P, S, idx, first)
     assert lengths[0, :16].tolist() == DEGREES and int(lengths[:, 16:].sum()) == 0
+    want = rigidity_ref.ordered(P, idx, first["resid"])
+    print(f"dP: {int((first['dP'] != want).sum())} elements differ from the documented order's bits")
+    assert torch.equal(first["dP"], want)
     for lo, hi in ((0, rigidity_ref.LANE_MAX), (rigidity_ref.LANE_MAX + 1, rigidity_ref.WAVE_MAX), (rigidity_ref.WAVE_MAX + 1, 10 ** 9)):
         assert any(lo <= t <= hi for t in DEGREES)
     again = _run(P, S, idx)
