@@ -34,8 +34,28 @@ def fix_coord_system(points: torch.Tensor) -> torch.Tensor:
     return torch.stack([points[..., 0], -points[..., 2], points[..., 1]], dim=-1).contiguous()
 
 
-def random_subset(batch: int, n_full: int, n_keep: int, device, generator=None) -> torch.Tensor:
-    """Per-sample random permutation prefix (dataset/utils.py:41): int32 (batch, min(n_keep, n_full))."""
+_bijection_calls = 0
+
+
+def random_subset(batch: int, n_full: int, n_keep: int, device, generator=None, method: str = "sort", key=None) -> torch.Tensor:
+    """Per-sample random permutation prefix (dataset/utils.py:41): int32 (batch, min(n_keep, n_full)).
+    ``method="sort"`` (the default) sorts ``batch x n_full`` random keys; ``method="bijection"`` draws the rows through
+    nsdp_subset_draw (datastore.subset_draw: a keyed bijection, O(n_keep) per sample, n_full <= 2^20) -- other rows than the
+    sort's, as uniform for every purpose here.  ``key``: its (seed, epoch, step, stream); by default the generator's (or torch's)
+    initial seed, epoch 0, the number of such calls so far in this process, and the surface stream."""
+    if method == "bijection":
+        from . import datastore
+        global _bijection_calls
+        if key is None:
+            seed = generator.initial_seed() if generator is not None else torch.initial_seed()
+            key = (seed, 0, _bijection_calls, datastore.SURFACE)
+            _bijection_calls += 1
+        if n_full > datastore.MAX_ROWS:
+            raise ValueError(f"random_subset(method='bijection'): n_full = {n_full} is beyond {datastore.MAX_ROWS} rows")
+        counts = torch.full((batch,), n_full, dtype=torch.int32, device=device)
+        return datastore.subset_draw(counts, min(n_keep, n_full), *key)
+    if method != "sort":
+        raise ValueError(f"random_subset: method '{method}' is neither 'sort' nor 'bijection'")
     keys = torch.rand(batch, n_full, device=device, generator=generator)
     return keys.argsort(dim=1)[:, :min(n_keep, n_full)].to(torch.int32).contiguous()
 

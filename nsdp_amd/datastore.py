@@ -1,0 +1,477 @@
+"""A data set on disk, resident on the device: the reader of the reference's directory layout, the (canonical, source, target)
+pair rules of its two flow data sets, and a loader whose batches touch only the rows they keep.
+
+The reference reads six .npz files per SAMPLE on the host (dataset/dataset_deform4d_flow.py:137-264), 200 000 fp16 rows each, to
+keep a few thousand rows of them.  An MI355X holds the data set: ``SampleStore`` loads every distinct frame ONCE, in the files' own
+number format, into two packed device arenas (include/nsdp_batch.h: point and normal of a surface row share a record) beside a
+frame table with each frame's first record, row counts and the bounding box of its FULL surface cloud -- what the handle mask
+needs (:209, "before sub-sampling"), so a batch needs no reduction.  A batch is then two kinds of launches: ``nsdp_subset_draw``
+(distinct random rows by a keyed bijection: no sort of ``B x N_full`` keys) and ``nsdp_batch_assemble`` (every tensor of
+``dataset.prepare_batch`` for the whole batch).  Nothing is read back and nothing synchronises per batch; the frame ids and row
+counts of a whole epoch go up in one copy.
+
+Every rank of a data-parallel job holds the WHOLE store (each rank's loader takes its share of the batches, ``shard``); a store
+larger than its byte budget is refused, by name, before anything is allocated on the device.
+
+Out of scope, refused by name: the user-handle data sets (``tosca``, ``dogrec``) and ``load_mesh`` (they need meshes),
+``partial_shape_ratio < 1`` (the reference's own call site cannot run, see dataset.py), stores larger than device memory.
+"""
+from __future__ import annotations
+
+import ctypes
+import os
+import random
+import zipfile
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+import torch
+
+from . import cpu_budget
+from ._lib import NsdpHipError, check, iptr, lib, on_device, optptr, stream_ptr
+
+SURFACE, SPACE = 0, 1                  # nsdp_subset_draw's `which`
+MAX_ROWS = 1 << 20                     # NSDP_BATCH_MAX_ROWS
+SURFACE_RECORD, SPACE_RECORD = 6, 4    # elements per arena record
+_KEYS = ("cano", "src", "tgt")
+
+
+class DataStoreError(ValueError):
+    pass
+
+
+# ---------------------------------------------------------------------------------------------------------------- pair rules
+def _read_split(cfg_data, split):
+    path = os.path.join(cfg_data["split_dir"], cfg_data["type"], split + ".lst")
+    if not os.path.isfile(path):
+        raise DataStoreError(f"SampleStore: missing split list {path}")
+    with open(path) as f:
+        return f.read().split("\n")
+
+
+def _frame_names(cfg_data, seq):
+    names = sorted(os.listdir(os.path.join(cfg_data["dataset_dir"], seq)))
+    return [n for n in names if int(n) % cfg_data["interval"] == 0]
+
+
+def _is_seq(cfg_data, name):
+    return name != "" and os.path.isdir(os.path.join(cfg_data["dataset_dir"], name))
+
+
+def form_pairs(cfg_data: dict, iden_split: str, motion_split: str) -> list:
+    """``all_deform_pairs`` before any shuffle, as the reference's ``_load`` forms them: a list of ``pair_info`` tuples
+    (idx_cano, cano sequence, cano frame, idx_motion, source sequence, source frame, target sequence, target frame).
+    ``deform4d``: dataset_deform4d_flow.py:37-117; ``deformtransfer``: dataset_deformtransfer_flow.py:38-116 (no identity list:
+    a sequence is its own canonical sequence; ``arbitrary`` has the evaluation rule only, with the per-animal source frame)."""
+    kind = cfg_data["type"]
+    train = motion_split[:5] == "train"
+    motion_names = _read_split(cfg_data, motion_split)
+    motion_dirs = sorted(n for n in motion_names if _is_seq(cfg_data, n))       # (sorting the joined paths sorts the names)
+    motion_index = {n: i for i, n in enumerate(motion_dirs)}
+    cano_of = {}
+    if kind == "deform4d":
+        iden_dirs = sorted(n for n in _read_split(cfg_data, iden_split) if _is_seq(cfg_data, n))
+        for i, seq in enumerate(iden_dirs):
+            cano_of[seq.split("_")[0]] = (i, seq)                                # (a later sequence of one identity wins, as there)
+    pairs = []
+    for seq in motion_names:
+        if not _is_seq(cfg_data, seq):
+            continue
+        if kind == "deform4d":
+            iden = seq.split("_")[0]
+            if iden not in cano_of:
+                continue
+            idx_cano, cano_seq = cano_of[iden]
+        else:
+            idx_cano, cano_seq = motion_index[seq], seq
+        idx_motion = motion_index[seq]
+        frames = _frame_names(cfg_data, seq)
+        if cfg_data["arbitrary"]:
+            if kind == "deform4d" and train:
+                for f0 in frames:
+                    for f1 in frames:
+                        pairs.append((idx_cano, cano_seq, "0000", idx_motion, seq, f0, seq, f1))
+            else:
+                if kind == "deform4d":
+                    first = "0000"
+                elif "cat" in seq or "lion" in seq:
+                    first = "0003"
+                elif "horse" in seq:
+                    first = "0005"
+                else:
+                    first = "0001"
+                for f in frames:
+                    if int(f) > 0:
+                        pairs.append((idx_cano, cano_seq, "0000", idx_motion, seq, first, seq, f))
+        else:
+            for f in frames:
+                pairs.append((idx_cano, cano_seq, "0000", idx_motion, cano_seq, "0000", seq, f))
+    return pairs
+
+
+def shuffle_order(order: list, num_sampled_pairs: int = -1):
+    """``random_shuffle_samples`` (:124-129) on a list, in place: ``random.Random(100).shuffle`` -- the permutation depends on the
+    length alone -- and the prefix of ``num_sampled_pairs`` (all of it unless positive).  Returns the sampled list."""
+    random.Random(100).shuffle(order)
+    return order[:num_sampled_pairs] if num_sampled_pairs > 0 else order
+
+
+def epoch_permutation(seed: int, epoch: int, count: int) -> np.ndarray:
+    """What ``DataLoader(shuffle=True)`` becomes: a host permutation of ``count`` samples, a function of (seed, epoch) alone."""
+    return np.random.Generator(np.random.PCG64([int(seed) & 0xFFFFFFFFFFFFFFFF, int(epoch), 0x4E534450])).permutation(count)
+
+
+# ---------------------------------------------------------------------------------------------------------------- files
+def _npz_member_header(path, key):
+    """(shape, dtype) of array ``key`` of an .npz file, from the member's header alone."""
+    if not os.path.isfile(path):
+        raise DataStoreError(f"SampleStore: missing file {path}")
+    with zipfile.ZipFile(path) as z:
+        if key + ".npy" not in z.namelist():
+            raise DataStoreError(f"SampleStore: {path} has no array '{key}'")
+        with z.open(key + ".npy") as f:
+            version = np.lib.format.read_magic(f)
+            read = np.lib.format.read_array_header_1_0 if version == (1, 0) else np.lib.format.read_array_header_2_0
+            shape, _, dtype = read(f)
+    return tuple(shape), np.dtype(dtype)
+
+
+def _fix_coord_system(p):
+    """dataset/utils.py:29-32: (x, y, z) -> (x, -z, y); a negation and a move: exact in every format."""
+    return np.stack([p[:, 0], -p[:, 2], p[:, 1]], axis=1)
+
+
+class _Frame:
+    __slots__ = ("seq", "name", "dir", "surf_rows", "space_rows", "surf_dtypes", "space_dtype", "surf_first", "space_first")
+
+
+# ---------------------------------------------------------------------------------------------------------------- launches
+def subset_draw(n_full: torch.Tensor, n_keep: int, seed: int, epoch: int, step: int, which: int) -> torch.Tensor:
+    """``n_keep`` DISTINCT rows of [0, n_full[b]) for every sample b, without sorting (nsdp_subset_draw): n_full (B,) int32 on the
+    device -> int32 (B, n_keep).  A function of (seed, epoch, step, b, which) -- tests/subset_ref.py reproduces it in numpy."""
+    B = n_full.shape[0]
+    out = torch.empty((B, int(n_keep)), dtype=torch.int32, device=n_full.device)
+    with on_device(n_full):
+        check(lib().nsdp_subset_draw(iptr(n_full, "n_full"), ctypes.c_int(B), ctypes.c_int(int(n_keep)),
+                                     ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), ctypes.c_uint32(int(epoch) & 0xFFFFFFFF),
+                                     ctypes.c_uint32(int(step) & 0xFFFFFFFF), ctypes.c_int(int(which)), iptr(out, "rows_out"),
+                                     stream_ptr()), "nsdp_subset_draw")
+    return out
+
+
+def _arena_ptr(t, name):
+    if not t.is_cuda or not t.is_contiguous() or t.dtype not in (torch.float16, torch.float32):
+        raise NsdpHipError(f"{name} must be a contiguous fp16 / fp32 GPU tensor (CPU not supported, no fallback)")
+    return ctypes.c_void_p(t.data_ptr())
+
+
+def batch_assemble(surface_arena, space_arena, frame_table, frame_ids, surf_idx, space_idx, m, partial_range, noise=None,
+                   noise_level=0.0) -> dict:
+    """nsdp_batch_assemble: the arenas (rows, 6) / (rows, 4) fp16 or fp32, frame_table (F, 6) int64, frame_ids (3, B) int32
+    (cano, src, tgt: ``inverse`` already applied), surf_idx (B, n) int32, space_idx (B, m) int32 or None (rows 0 .. m-1) -> the
+    data_dict of ``dataset.prepare_batch``."""
+    B, n = surf_idx.shape
+    dev = surf_idx.device
+    if frame_table.dtype != torch.int64 or not frame_table.is_contiguous() or not frame_table.is_cuda:
+        raise NsdpHipError("frame_table must be a contiguous int64 GPU tensor")
+    if noise is not None and tuple(noise.shape) != (B, n, 3):
+        raise NsdpHipError(f"noise must be [B, n, 3] = {(B, n, 3)}, got {tuple(noise.shape)}")
+    if space_idx is not None:
+        m = space_idx.shape[1]
+    surface = torch.empty((6, B, n, 3), dtype=torch.float32, device=dev)
+    handle = torch.empty((B, n, 1), dtype=torch.uint8, device=dev)
+    inputs = torch.empty((B, n, 7), dtype=torch.float32, device=dev)
+    space = torch.empty((3, B, int(m), 3), dtype=torch.float32, device=dev)
+    with on_device(surf_idx):
+        check(lib().nsdp_batch_assemble(
+            _arena_ptr(surface_arena, "surface_arena"), ctypes.c_longlong(surface_arena.shape[0]),
+            ctypes.c_int(surface_arena.dtype == torch.float16), _arena_ptr(space_arena, "space_arena"),
+            ctypes.c_longlong(space_arena.shape[0]), ctypes.c_int(space_arena.dtype == torch.float16),
+            ctypes.c_void_p(frame_table.data_ptr()), ctypes.c_int(frame_table.shape[0]), iptr(frame_ids, "frame_ids"), ctypes.c_int(B),
+            iptr(surf_idx, "surf_idx"), ctypes.c_int(n), optptr(None) if space_idx is None else iptr(space_idx, "space_idx"),
+            ctypes.c_int(int(m)), ctypes.c_float(partial_range), optptr(None) if noise is None else ctypes.c_void_p(_f32(noise).data_ptr()),
+            ctypes.c_float(noise_level), ctypes.c_void_p(surface.data_ptr()), ctypes.c_void_p(handle.data_ptr()),
+            ctypes.c_void_p(inputs.data_ptr()), ctypes.c_void_p(space.data_ptr()), stream_ptr()), "nsdp_batch_assemble")
+    out = {}
+    for k, key in enumerate(("surface_samples", "surface_normals")):
+        for i, name in enumerate(_KEYS):
+            out[f"{key}_{name}"] = surface[3 * k + i]
+    out["cano_handle_sample_idx"] = handle.view(torch.bool)
+    out["surface_samples_inputs"] = inputs
+    for i, name in enumerate(_KEYS):
+        out[f"space_samples_{name}"] = space[i]
+    return out
+
+
+def _f32(t):
+    if t.dtype != torch.float32 or not t.is_contiguous() or not t.is_cuda:
+        raise NsdpHipError("noise must be a contiguous float32 GPU tensor")
+    return t
+
+
+# ---------------------------------------------------------------------------------------------------------------- the store
+class SampleStore:
+    """The frames of ``config["data"]`` that the pairs of (iden_split, motion_split) reference, on ``device``.
+
+    ``pairs``: the pair_info tuples in the reference's ``all_deform_pairs`` order before its first shuffle; ``sample_indices(e)``:
+    the positions (into ``pairs``) of ``sample_deform_pairs`` during epoch ``e`` -- the reference reshuffles when the last index of
+    a train split is fetched, here that happens at the end of each epoch.  Each rank of a data-parallel job holds the whole store.
+    ``byte_budget``: the most device memory the arenas may take (default: half of the device's memory)."""
+
+    def __init__(self, config, iden_split, motion_split, num_sampled_pairs=-1, device="cuda", load_mesh=False, byte_budget=None,
+                 pairs_only=False):
+        data = config["data"]
+        self.cfg_data, self.iden_split, self.motion_split = data, iden_split, motion_split
+        self.num_sampled_pairs = int(num_sampled_pairs)
+        self.is_train = motion_split[:5] == "train"
+        kind = data.get("type")
+        if kind in ("tosca", "dogrec"):
+            raise DataStoreError(f"SampleStore: data type '{kind}' (the user-handle data sets) needs meshes and is not supported")
+        if kind not in ("deform4d", "deformtransfer"):
+            raise DataStoreError(f"SampleStore: unknown data type '{kind}' (deform4d and deformtransfer are read)")
+        if load_mesh:
+            raise DataStoreError("SampleStore: load_mesh is not supported (meshes are not read from a data set)")
+        if data.get("partial_shape_ratio", 1.0) < 1.0:
+            raise DataStoreError("SampleStore: partial_shape_ratio < 1 is not supported from disk (the reference's own call site "
+                                 "cannot run, see nsdp_amd/dataset.py)")
+        if not os.path.isdir(data["dataset_dir"]):
+            raise DataStoreError(f"SampleStore: missing dataset_dir {data['dataset_dir']}")
+        self.pairs = form_pairs(data, iden_split, motion_split)
+        if not self.pairs:
+            raise DataStoreError(f"SampleStore: the splits '{iden_split}' / '{motion_split}' form no deformation pair")
+        self._orders = []                 # _orders[k]: `all_deform_pairs` as positions into self.pairs after k + 1 shuffles
+        self.n = int(data["num_surf_samples"])
+        if pairs_only:
+            return
+        self.device = torch.device(device)
+        self._index_frames()
+        self._judge(byte_budget)
+        self._load()
+
+    # -------------------------------------------------------------------------------------------------------- sample lists
+    def sample_indices(self, epoch: int = 0) -> list:
+        """Positions into ``pairs`` of the samples of epoch ``epoch`` (the prefix of num_sampled_pairs after epoch + 1 shuffles of
+        a train split or of a sampled one; a sampled non-train split is shuffled once; else the list as it was formed)."""
+        if not (self.is_train or self.num_sampled_pairs > 0):
+            return list(range(len(self.pairs)))
+        order = self.order_after(epoch + 1 if self.is_train else 1)
+        return order[:self.num_sampled_pairs] if self.num_sampled_pairs > 0 else order
+
+    def order_after(self, shuffles: int) -> list:
+        """``all_deform_pairs`` as positions into ``pairs`` after ``shuffles`` calls of ``random_shuffle_samples``."""
+        while len(self._orders) < shuffles:
+            order = list(self._orders[-1]) if self._orders else list(range(len(self.pairs)))
+            shuffle_order(order)
+            self._orders.append(order)
+        return self._orders[shuffles - 1] if shuffles > 0 else list(range(len(self.pairs)))
+
+    def sample_pairs(self, epoch: int = 0) -> list:
+        return [self.pairs[i] for i in self.sample_indices(epoch)]
+
+    def __len__(self):
+        return len(self.sample_indices(0))
+
+    # -------------------------------------------------------------------------------------------------------- frames
+    def _index_frames(self):
+        self.frames, self._frame_id = [], {}
+        ids = np.empty((len(self.pairs), 3), dtype=np.int32)
+        for p, info in enumerate(self.pairs):
+            for c, (seq, name) in enumerate(((info[1], info[2]), (info[4], info[5]), (info[6], info[7]))):
+                if (seq, name) not in self._frame_id:
+                    fr = _Frame()
+                    fr.seq, fr.name, fr.dir = seq, name, os.path.join(self.cfg_data["dataset_dir"], seq, name)
+                    self._frame_id[(seq, name)] = len(self.frames)
+                    self.frames.append(fr)
+                ids[p, c] = self._frame_id[(seq, name)]
+        self.pair_frames = ids
+
+    def _workers(self):
+        return max(1, min(16, cpu_budget.cpu_budget()))
+
+    def _judge(self, byte_budget):
+        """Everything that is refused, from the files' headers: nothing has been allocated yet."""
+        data = self.cfg_data
+
+        def header(fr):
+            if not os.path.isdir(fr.dir):
+                raise DataStoreError(f"SampleStore: missing frame directory {fr.dir}")
+            sp, dp = _npz_member_header(os.path.join(fr.dir, data["surface_flow_file"]), "points")
+            sn, dn = _npz_member_header(os.path.join(fr.dir, data["surface_flow_file"]), "normals")
+            qp, dq = _npz_member_header(os.path.join(fr.dir, data["space_flow_file"]), "points")
+            for shape, what in ((sp, "surface points"), (sn, "surface normals"), (qp, "space points")):
+                if len(shape) != 2 or shape[1] != 3:
+                    raise DataStoreError(f"SampleStore: {what} of {fr.dir} have shape {shape}, not (rows, 3)")
+            if sp != sn:
+                raise DataStoreError(f"SampleStore: {fr.dir} has {sp[0]} surface points but {sn[0]} surface normals")
+            fr.surf_rows, fr.space_rows, fr.surf_dtypes, fr.space_dtype = sp[0], qp[0], (dp, dn), dq
+            return fr
+
+        with ThreadPoolExecutor(max_workers=self._workers()) as ex:
+            list(ex.map(header, self.frames))
+        for fr in self.frames:
+            if fr.surf_rows > MAX_ROWS or fr.space_rows > MAX_ROWS:
+                raise DataStoreError(f"SampleStore: frame {fr.dir} has {fr.surf_rows} surface / {fr.space_rows} space rows, more "
+                                     f"than the {MAX_ROWS} a frame may hold")
+            if fr.surf_rows < self.n:
+                raise DataStoreError(f"SampleStore: frame {fr.dir} has {fr.surf_rows} surface rows, fewer than num_surf_samples = {self.n}")
+        for info, (c, s, t) in zip(self.pairs, self.pair_frames):
+            rows = [self.frames[i].surf_rows for i in (c, s, t)]
+            if len(set(rows)) != 1:
+                raise DataStoreError(f"SampleStore: the frames of pair {info[1]}/{info[2]}, {info[4]}/{info[5]}, {info[6]}/{info[7]} differ "
+                                     f"in surface count ({rows}); the row indices are correspondences")
+            rows = [self.frames[i].space_rows for i in (c, s, t)]
+            if len(set(rows)) != 1:
+                raise DataStoreError(f"SampleStore: the frames of pair {info[1]}/{info[2]}, {info[4]}/{info[5]}, {info[6]}/{info[7]} differ "
+                                     f"in space count ({rows}); the row indices are correspondences")
+        want = int(data["num_space_samples"])
+        counts = sorted({fr.space_rows for fr in self.frames})
+        if counts[0] > want:
+            self.m, self.draw_space = want, True
+        elif len(counts) == 1:
+            self.m, self.draw_space = counts[0], False          # (utils.py:49: not more than requested -> every row, in order)
+        else:
+            raise DataStoreError(f"SampleStore: the frames' space counts ({counts[0]} .. {counts[-1]}) are neither all above "
+                                 f"num_space_samples = {want} nor all equal; such samples cannot be stacked into a batch")
+        f16 = np.dtype(np.float16)
+        ok = (f16, np.dtype(np.float32))
+        for fr in self.frames:
+            for dt in fr.surf_dtypes + (fr.space_dtype,):
+                if dt not in ok:
+                    raise DataStoreError(f"SampleStore: {fr.dir} holds {dt} arrays; float16 and float32 are read")
+        self.surface_dtype = torch.float16 if all(d == f16 for fr in self.frames for d in fr.surf_dtypes) else torch.float32
+        self.space_dtype = torch.float16 if all(fr.space_dtype == f16 for fr in self.frames) else torch.float32
+        self.surface_rows = sum(fr.surf_rows for fr in self.frames)
+        self.space_rows = sum(fr.space_rows for fr in self.frames)
+        self.nbytes = (self.surface_rows * SURFACE_RECORD * (2 if self.surface_dtype == torch.float16 else 4)
+                       + self.space_rows * SPACE_RECORD * (2 if self.space_dtype == torch.float16 else 4) + 48 * len(self.frames))
+        if byte_budget is None:
+            if self.device.type != "cuda":
+                raise NsdpHipError("SampleStore needs a GPU device (CPU not supported, no fallback)")
+            byte_budget = torch.cuda.get_device_properties(self.device).total_memory // 2
+        self.byte_budget = int(byte_budget)
+        if self.nbytes > self.byte_budget:
+            raise DataStoreError(f"SampleStore: {len(self.frames)} frames need {self.nbytes} bytes on the device, more than the "
+                                 f"byte budget of {self.byte_budget} bytes (a store larger than device memory is not supported)")
+
+    def _load(self):
+        if self.device.type != "cuda":
+            raise NsdpHipError("SampleStore needs a GPU device (CPU not supported, no fallback)")
+        data = self.cfg_data
+        fix = bool(data["fix_coord_system"])
+        np_surf = np.float16 if self.surface_dtype == torch.float16 else np.float32
+        np_space = np.float16 if self.space_dtype == torch.float16 else np.float32
+        first_s = first_q = 0
+        for fr in self.frames:
+            fr.surf_first, fr.space_first = first_s, first_q
+            first_s, first_q = first_s + fr.surf_rows, first_q + fr.space_rows
+        self.surface_arena = torch.empty((self.surface_rows, SURFACE_RECORD), dtype=self.surface_dtype, device=self.device)
+        self.space_arena = torch.empty((self.space_rows, SPACE_RECORD), dtype=self.space_dtype, device=self.device)
+        table = np.zeros((len(self.frames), 6), dtype=np.int64)
+
+        def read(k):
+            fr = self.frames[k]
+            with np.load(os.path.join(fr.dir, data["surface_flow_file"])) as z:
+                pts, nrm = z["points"], z["normals"]
+            with np.load(os.path.join(fr.dir, data["space_flow_file"])) as z:
+                spc = z["points"]
+            if fix:
+                pts, nrm, spc = _fix_coord_system(pts), _fix_coord_system(nrm), _fix_coord_system(spc)
+            surf = np.concatenate([pts.astype(np_surf, copy=False), nrm.astype(np_surf, copy=False)], axis=1)
+            space = np.zeros((spc.shape[0], SPACE_RECORD), dtype=np_space)
+            space[:, :3] = spc
+            p32 = pts.astype(np.float32)
+            box = np.concatenate([p32.min(axis=0), p32.max(axis=0)]) if len(p32) else np.zeros(6, np.float32)
+            return k, surf, space, box.astype(np.float32)
+
+        with ThreadPoolExecutor(max_workers=self._workers()) as ex:
+            for k, surf, space, box in ex.map(read, range(len(self.frames))):
+                fr = self.frames[k]
+                self.surface_arena[fr.surf_first:fr.surf_first + fr.surf_rows].copy_(torch.from_numpy(surf))
+                self.space_arena[fr.space_first:fr.space_first + fr.space_rows].copy_(torch.from_numpy(space))
+                table[k, 0], table[k, 1] = fr.surf_first, fr.space_first
+                table[k, 2] = fr.surf_rows | (fr.space_rows << 32)
+                table[k, 3:6] = box.view(np.int64)
+        self.frame_table_host = table
+        self.frame_table = torch.from_numpy(table).to(self.device)
+        self.surf_counts = np.array([fr.surf_rows for fr in self.frames], dtype=np.int32)
+        self.space_counts = np.array([fr.space_rows for fr in self.frames], dtype=np.int32)
+
+    # -------------------------------------------------------------------------------------------------------- batches
+    def frame_bbox(self, frame_id):
+        """(bbox_min, bbox_max) float32 of a frame's full surface cloud, from the host copy of the frame table."""
+        box = self.frame_table_host[frame_id, 3:6].copy().view(np.float32)
+        return box[:3], box[3:]
+
+    def frame_arrays(self, frame_id):
+        """A frame's arrays as fp32 device tensors {surface_samples, surface_normals, space_samples} (for tests and tools)."""
+        fr = self.frames[frame_id]
+        s = self.surface_arena[fr.surf_first:fr.surf_first + fr.surf_rows].float()
+        q = self.space_arena[fr.space_first:fr.space_first + fr.space_rows].float()
+        return {"surface_samples": s[:, :3].contiguous(), "surface_normals": s[:, 3:].contiguous(), "space_samples": q[:, :3].contiguous()}
+
+    def assemble(self, frame_ids, surf_idx, space_idx=None, noise=None) -> dict:
+        """The data_dict of the samples whose (cano, src, tgt) frames are ``frame_ids`` (3, B) int32 on the device, as the pairs
+        list them: ``inverse`` is applied here, as ``prepare_batch`` applies it."""
+        data = self.cfg_data
+        if not data["arbitrary"] and data["inverse"]:
+            frame_ids = frame_ids[[0, 2, 1]].contiguous()
+        level = float(data["noise_level"])
+        if level > 0.0 and noise is None:
+            raise DataStoreError("SampleStore.assemble: noise_level > 0 needs a noise tensor")
+        return batch_assemble(self.surface_arena, self.space_arena, self.frame_table, frame_ids, surf_idx, space_idx, self.m,
+                              float(data["partial_range"]), noise if level > 0.0 else None, level)
+
+    def loader(self, batch, seed, noise_generator=None, shuffle=None):
+        return StoreLoader(self, batch, seed, noise_generator, shuffle)
+
+
+class StoreLoader:
+    """An iterable of data_dict batches on the store's device; every pass over it is one epoch (its number counts up from 0).
+    ``shuffle`` (default: train splits) orders an epoch's samples by ``epoch_permutation(seed, epoch)``; the row subsets of batch
+    ``step`` of epoch ``epoch`` are nsdp_subset_draw's for (seed, epoch, step), so two loaders with one seed give equal batches.
+    The last partial batch of an epoch is yielded as it is.  ``noise_generator``: a torch.Generator on the device for the
+    source noise (``noise_level > 0``)."""
+
+    def __init__(self, store, batch, seed, noise_generator=None, shuffle=None):
+        if int(batch) < 1:
+            raise DataStoreError(f"StoreLoader: batch = {batch} must be positive")
+        self.store, self.batch, self.seed, self.noise_generator = store, int(batch), int(seed), noise_generator
+        self.shuffle = store.is_train if shuffle is None else bool(shuffle)
+        self.epoch = 0
+
+    def __len__(self):
+        return -(-len(self.store) // self.batch)
+
+    def epoch_samples(self, epoch):
+        """Positions into ``store.pairs`` of the epoch's samples, in the order they are batched."""
+        samples = np.asarray(self.store.sample_indices(epoch), dtype=np.int64)
+        if self.shuffle:
+            samples = samples[epoch_permutation(self.seed, epoch, len(samples))]
+        return samples
+
+    def _batches(self, steps):
+        st = self.store
+        epoch, self.epoch = self.epoch, self.epoch + 1
+        samples = self.epoch_samples(epoch)
+        ids = st.pair_frames[samples]                                                     # (E, 3)
+        plan = np.concatenate([ids.T, st.surf_counts[ids[:, 0]][None], st.space_counts[ids[:, 0]][None]], axis=0)
+        plan = torch.from_numpy(np.ascontiguousarray(plan, dtype=np.int32)).to(st.device, non_blocking=True)      # one copy per epoch
+        level = float(st.cfg_data["noise_level"])
+        for step in steps:
+            lo, hi = step * self.batch, min((step + 1) * self.batch, len(samples))
+            frame_ids = plan[:3, lo:hi].contiguous()
+            surf_idx = subset_draw(plan[3, lo:hi].contiguous(), st.n, self.seed, epoch, step, SURFACE)
+            space_idx = subset_draw(plan[4, lo:hi].contiguous(), st.m, self.seed, epoch, step, SPACE) if st.draw_space else None
+            noise = None
+            if level > 0.0:
+                noise = torch.randn((hi - lo, st.n, 3), device=st.device, generator=self.noise_generator)
+            yield st.assemble(frame_ids, surf_idx, space_idx, noise)
+
+    def __iter__(self):
+        return self._batches(range(len(self)))
+
+    def shard(self, rank, world_size):
+        """This rank's share of an epoch, with ``SyntheticLoader.shard``'s meaning: of every ``world_size`` consecutive batches the
+        rank-th; a trailing partial group is dropped so that all ranks take the same number of steps."""
+        groups = len(self) // world_size
+        return self._batches([g * world_size + rank for g in range(groups)])

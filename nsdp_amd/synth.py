@@ -105,3 +105,84 @@ def procedural_state_dict(template: dict, seed: int) -> dict:
         else:
             raise KeyError(f"unhandled state_dict entry {key} {shape}")
     return out
+
+
+def _per_identity(value, identities, what):
+    if isinstance(value, dict):
+        return {k: int(value[k]) for k in identities}
+    if isinstance(value, (list, tuple)):
+        if len(value) != len(identities):
+            raise ValueError(f"write_dataset_tree: {what} has {len(value)} entries for {len(identities)} identities")
+        return {k: int(v) for k, v in zip(identities, value)}
+    return {k: int(value) for k in identities}
+
+
+def dataset_tree_frame(seed: int, identity: str, motion: str, frame: int, frames: int, n_surface: int, n_space: int):
+    """The procedural arrays of one frame (float32): surface points, surface normals, space points.  Row i of every frame of an
+    identity is the same material point (the reference's files are correspondences); frame 0 of every motion is the identity's
+    canonical pose, later frames add a smooth, motion-specific displacement that grows with the frame number."""
+    t = frame / max(frames - 1, 1)
+    w = uniform(seed, f"{motion}/wave", (3, 3), -1.0, 1.0).astype(np.float64)
+    amp = uniform(seed, f"{motion}/amp", (3,), 0.03, 0.08).astype(np.float64)
+
+    def move(p):
+        return p + t * amp[None, :] * np.sin(2.0 * np.pi * (p @ w.T) + 0.5)
+
+    surf = uniform(seed, f"{identity}/surface", (n_surface, 3), -0.5, 0.5).astype(np.float64)
+    nrm = normal(seed, f"{identity}/normals", (n_surface, 3)).astype(np.float64)
+    nrm = nrm + 0.3 * t * np.cos(2.0 * np.pi * (surf @ w.T))
+    nrm /= np.maximum(np.linalg.norm(nrm, axis=1, keepdims=True), 1e-6)
+    space = uniform(seed, f"{identity}/space", (n_space, 3), -0.5, 0.5).astype(np.float64)
+    return move(surf).astype(np.float32), nrm.astype(np.float32), move(space).astype(np.float32)
+
+
+def write_dataset_tree(root, identities, motions, frames, n_surface, n_space, dtype=np.float16, data_type="deform4d", seed=0,
+                       held_out_motions=1, surface_flow_file="surface_points.npz", space_flow_file="flow.npz",
+                       norm_params_file="orig_to_gaps.txt"):
+    """Write a procedural data set in the reference's directory layout (dataset/dataset_deform4d_flow.py:37-172) and return the
+    ``data`` section of a config that reads it:
+
+        root/dataset/<sequence>/<frame %04d>/{surface_flow_file (points, normals), space_flow_file (points), norm_params_file}
+        root/splits/<data_type>/{identity_seen, train_seen, test_unseen_motions}.lst
+
+    ``identities`` / ``motions``: names (without '_' or '-').  A sequence is ``identity_motion`` for ``deform4d`` and
+    ``identity-motion`` for ``deformtransfer`` (whose source frame depends on the animal in the name: 0003 for cat and lion, 0005
+    for horse, else 0001).  ``n_surface`` / ``n_space``: one count, or one per identity (list or dict).  ``dtype``: the files'
+    (numpy float16 or float32; a dict per identity is accepted too).  ``identity_seen`` lists the first motion's sequence of every
+    identity (its frame 0000 is the canonical pose), ``train_seen`` every sequence but those of the last ``held_out_motions``
+    motions, ``test_unseen_motions`` the rest (all of them when nothing is left).  norm_params_file holds the identity matrix."""
+    import os
+    identities, motions = [str(i) for i in identities], [str(m) for m in motions]
+    sep = {"deform4d": "_", "deformtransfer": "-"}.get(data_type)
+    if sep is None:
+        raise ValueError(f"write_dataset_tree: data_type '{data_type}' is neither 'deform4d' nor 'deformtransfer'")
+    for name in identities + motions:
+        if "_" in name or "-" in name or not name:
+            raise ValueError(f"write_dataset_tree: the name '{name}' must be non-empty and free of '_' and '-'")
+    ns, nq = _per_identity(n_surface, identities, "n_surface"), _per_identity(n_space, identities, "n_space")
+    dts = dtype if isinstance(dtype, dict) else {k: dtype for k in identities}
+    dataset_dir, split_dir = os.path.join(root, "dataset"), os.path.join(root, "splits")
+    for iden in identities:
+        dt = np.dtype(dts[iden])
+        if dt not in (np.dtype(np.float16), np.dtype(np.float32)):
+            raise ValueError(f"write_dataset_tree: dtype {dt} is neither float16 nor float32")
+        for motion in motions:
+            for f in range(int(frames)):
+                d = os.path.join(dataset_dir, iden + sep + motion, "%04d" % f)
+                os.makedirs(d, exist_ok=True)
+                surf, nrm, space = dataset_tree_frame(seed, iden, motion, f, int(frames), ns[iden], nq[iden])
+                np.savez(os.path.join(d, surface_flow_file), points=surf.astype(dt), normals=nrm.astype(dt))
+                np.savez(os.path.join(d, space_flow_file), points=space.astype(dt))
+                np.savetxt(os.path.join(d, norm_params_file), np.eye(4))
+    os.makedirs(os.path.join(split_dir, data_type), exist_ok=True)
+    held = motions[len(motions) - int(held_out_motions):] if 0 < int(held_out_motions) < len(motions) else []
+    lists = {"identity_seen": [i + sep + motions[0] for i in identities],
+             "train_seen": [i + sep + m for i in identities for m in motions if m not in held],
+             "test_unseen_motions": [i + sep + m for i in identities for m in (held or motions)]}
+    for name, seqs in lists.items():
+        with open(os.path.join(split_dir, data_type, name + ".lst"), "w") as f:
+            f.write("\n".join(seqs) + "\n")
+    return {"type": data_type, "dataset_dir": dataset_dir, "split_dir": split_dir, "interval": 1, "arbitrary": False,
+            "inverse": False, "fix_coord_system": False, "num_surf_samples": min(ns.values()), "num_space_samples": min(nq.values()),
+            "partial_range": 0.1, "noise_level": 0.0, "partial_shape_ratio": 1.0, "norm_params_file": norm_params_file,
+            "surface_flow_file": surface_flow_file, "space_flow_file": space_flow_file}

@@ -1,10 +1,14 @@
 """Training harness around the MI355X TDNet path with the loop semantics of the reference's train.py (SURVEY.md
 section 8 next-1): seeding, epoch-wise step learning rate, checkpoint cadence, validation cadence and best-model
 tracking are the reference's; the model, its train/validate functions and the optimizer come from
-``nsdp_amd.model``.  The data loader is whatever yields the reference's ``data_dict`` batches; ``--synthetic`` uses
-procedural batches (the dataset readers are outside this round's scope).
+``nsdp_amd.model``.  The data loader is whatever yields the reference's ``data_dict`` batches: ``--dataset`` trains from the
+data set on disk that ``config["data"]`` names (nsdp_amd.datastore: the reference's directory layout and pair rules, every
+frame resident on the device, the splits and batch sizes of the config's ``training`` / ``validation`` sections as in the
+reference's train.py:105-135); ``--synthetic`` (the default) uses procedural batches.  Not read from disk: the user-handle data
+sets (``tosca``, ``dogrec``), meshes (``load_mesh``), partial shapes, and a data set larger than the device's memory.
 
     python -m nsdp_amd.train config.yaml experiment_dir [--synthetic 4] [--epochs 2]
+    python -m nsdp_amd.train config.yaml experiment_dir --dataset [--graph] [--gpus N]
 """
 from __future__ import annotations
 
@@ -189,7 +193,12 @@ def main(argv=None):
     ap.add_argument("--weight_backward_file", default=None, help="overrides training.weight_backward_file")
     ap.add_argument("--continue_from_epoch", default=0, type=int)
     ap.add_argument("--seed", type=int, default=27)
-    ap.add_argument("--synthetic", type=int, default=4, help="procedural batches per epoch (no dataset readers yet)")
+    ap.add_argument("--synthetic", type=int, default=None, help="procedural batches per epoch (default 4; not with --dataset)")
+    ap.add_argument("--dataset", action="store_true",
+                    help="train from the data set on disk that the config's data section names (dataset_dir, split_dir, type "
+                         "deform4d / deformtransfer): splits, num_sampled_pairs and batch_size come from its training / validation "
+                         "sections; every frame is held on the device (each rank holds all of them).  Not with --synthetic; "
+                         "--batch, --surface, --queries and --uncorresponded describe procedural batches and are not used")
     ap.add_argument("--batch", type=int, default=8, help="shapes per batch = per GPU and step (the global batch is this x --gpus)")
     ap.add_argument("--surface", type=int, default=2048, help="surface samples per shape of the procedural batches (default 2048)")
     ap.add_argument("--queries", type=int, default=8192, help="query points per shape of the procedural batches (default 8192)")
@@ -206,6 +215,10 @@ def main(argv=None):
                          "the ranks are launched here; under torchrun (RANK / WORLD_SIZE set) this process is one of them")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend of the data-parallel job (nccl = RCCL)")
     args = ap.parse_args(argv)
+    if args.dataset and args.synthetic is not None:
+        sys.exit(f"nsdp_amd.train: --dataset and --synthetic {args.synthetic} were given together; choose one source of batches")
+    if args.synthetic is None:
+        args.synthetic = 4
     if args.surface < 1 or args.queries < 1:
         sys.exit(f"nsdp_amd.train: --surface {args.surface} and --queries {args.queries} must be positive")
     if args.uncorresponded is not None and not 1 <= args.uncorresponded <= args.queries:
@@ -252,11 +265,10 @@ def main(argv=None):
     if args.graph:
         from .graph_step import GraphedTrainOnBatch
         train_fn = GraphedTrainOnBatch(train_fn, reducer=dp.reducer if dp is not None else None)
-    # (one loader of world x synthetic batches: every rank builds the same list and takes its share, DataParallel.shard)
-    targets = {} if args.uncorresponded is None else {"uncorresponded": args.uncorresponded}
-    train = SyntheticLoader(args.seed, args.synthetic * world, args.batch, n_surf=args.surface, n_query=args.queries, **targets)
-    val = SyntheticLoader(args.seed + 10000, max(1, args.synthetic // 4) * world, args.batch, n_surf=args.surface,
-                          n_query=args.queries, **targets)
+    if args.dataset:
+        train, val = dataset_loaders(config, args.seed, device, log=say)
+    else:
+        train, val = synthetic_loaders(args, world)
     fit(model, (train_fn, val_fn), lr_scheduler, optimizer, train, val, config, args.experiment_directory, args, device,
         log=say, dp=dp)
     if dp is not None:
@@ -267,6 +279,31 @@ def main(argv=None):
         if not ok:
             return 1
     return 0
+
+
+def dataset_loaders(config, seed, device, log=print):
+    """The reference's train.py:105-135 over device-resident stores: (train loader, validation loader).  Every rank builds both
+    stores whole and takes its share of the batches (StoreLoader.shard); the validation loader does not shuffle."""
+    from .datastore import SampleStore
+    loaders = []
+    for section, default_batch, what in (("training", 16, "training"), ("validation", 1, "validation")):
+        sec = config[section]
+        store = SampleStore(config, sec["iden_split"], sec["motion_split"], num_sampled_pairs=sec.get("num_sampled_pairs", -1),
+                            device=device, load_mesh=sec.get("load_mesh", False))
+        log("Loaded {} {} deformation pairs ({} frames, {:.1f} MB on the device)".format(len(store), what, len(store.frames),
+                                                                                      store.nbytes / 1e6))
+        loaders.append(store.loader(sec.get("batch_size", default_batch), seed if section == "training" else seed + 10000,
+                                    noise_generator=None, shuffle=section == "training"))
+    return tuple(loaders)
+
+
+def synthetic_loaders(args, world):
+    # (one loader of world x synthetic batches: every rank builds the same list and takes its share, DataParallel.shard)
+    targets = {} if args.uncorresponded is None else {"uncorresponded": args.uncorresponded}
+    train = SyntheticLoader(args.seed, args.synthetic * world, args.batch, n_surf=args.surface, n_query=args.queries, **targets)
+    val = SyntheticLoader(args.seed + 10000, max(1, args.synthetic // 4) * world, args.batch, n_surf=args.surface,
+                          n_query=args.queries, **targets)
+    return train, val
 
 
 if __name__ == "__main__":
