@@ -21,6 +21,7 @@
 
 #include "../../include/nsdp_batch.h"
 #include "common.h"
+#include "draw_key.h"
 #include "prof.h"
 
 #pragma clang fp contract(off)
@@ -30,16 +31,8 @@ namespace {
 constexpr int kThreads = 256;
 constexpr int kRounds = 8;
 
-__host__ __device__ __forceinline__ uint32_t mix32(uint32_t x) {
-  x ^= x >> 16;
-  x *= 0x7FEB352Du;
-  x ^= x >> 15;
-  x *= 0x846CA68Bu;
-  x ^= x >> 16;
-  return x;
-}
-
-__host__ __device__ __forceinline__ uint32_t absorb(uint32_t h, uint32_t v) { return mix32((h ^ v) + 0x9E3779B9u); }
+using nsdp::absorb;      // (draw_key.h: shared with the other keyed draw)
+using nsdp::mix32;
 
 // `base`: the key after seed, epoch and step (host); rows_out[b, j] = pi_b(j mod n)
 __global__ __launch_bounds__(kThreads) void subset_draw_kernel(const int32_t *__restrict__ n_full, int n_keep, uint32_t base,
@@ -228,11 +221,7 @@ extern "C" int nsdp_subset_draw(const int32_t *n_full, int B, int n_keep, uint64
   if (B == 0 || n_keep == 0) return 0;
   NSDP_REQUIRE(n_full && rows_out, "subset_draw: null pointer");
   NSDP_REQUIRE(aligned(n_full, 4) && aligned(rows_out, 4), "subset_draw: a pointer is not 4-byte aligned");
-  uint32_t base = 0x4E534450u;
-  base = absorb(base, static_cast<uint32_t>(seed & 0xFFFFFFFFull));
-  base = absorb(base, static_cast<uint32_t>(seed >> 32));
-  base = absorb(base, epoch);
-  base = absorb(base, step);
+  const uint32_t base = nsdp::draw_base_key(seed, epoch, step);
   NSDP_TRACE("subset_draw<B=%d,n_keep=%d>", B, n_keep);
   hipLaunchKernelGGL(subset_draw_kernel, dim3(nsdp::ceil_div(n_keep, kThreads), B), dim3(kThreads), 0, nsdp::as_stream(stream),
                      n_full, n_keep, base, static_cast<uint32_t>(which), rows_out);

@@ -186,3 +186,80 @@ def write_dataset_tree(root, identities, motions, frames, n_surface, n_space, dt
             "inverse": False, "fix_coord_system": False, "num_surf_samples": min(ns.values()), "num_space_samples": min(nq.values()),
             "partial_range": 0.1, "noise_level": 0.0, "partial_shape_ratio": 1.0, "norm_params_file": norm_params_file,
             "surface_flow_file": surface_flow_file, "space_flow_file": space_flow_file}
+
+
+# ---------------------------------------------------------------------------------------------------------------- mesh trees
+def sphere_mesh(rings: int, segments: int, radius: float = 0.4):
+    """A closed latitude-longitude sphere: (verts float64 (rings * segments + 2, 3), faces int32 (2 * rings * segments, 3)), the
+    y axis through the poles.  rings = 100, segments = 200: 20 002 vertices and 40 000 faces."""
+    theta = np.pi * (np.arange(rings) + 1) / (rings + 1)
+    phi = 2.0 * np.pi * np.arange(segments) / segments
+    ring = np.stack([np.outer(np.sin(theta), np.cos(phi)), np.outer(np.cos(theta), np.ones(segments)),
+                     np.outer(np.sin(theta), np.sin(phi))], axis=2).reshape(-1, 3)
+    verts = radius * np.concatenate([ring, [[0.0, 1.0, 0.0], [0.0, -1.0, 0.0]]])
+    north, south = rings * segments, rings * segments + 1
+    i, j = np.meshgrid(np.arange(rings - 1), np.arange(segments), indexing="ij")
+    a, b = i * segments + j, i * segments + (j + 1) % segments
+    quads = np.concatenate([np.stack([a, a + segments, b], axis=2), np.stack([b, a + segments, b + segments], axis=2)]).reshape(-1, 3)
+    j = np.arange(segments)
+    caps = np.concatenate([np.stack([np.full(segments, north), j, (j + 1) % segments], axis=1),
+                           np.stack([np.full(segments, south), (rings - 1) * segments + (j + 1) % segments,
+                                     (rings - 1) * segments + j], axis=1)])
+    return verts, np.concatenate([quads, caps])[:, [0, 2, 1]].astype(np.int32)           # (outward normals)
+
+
+def mesh_tree_vertices(seed: int, verts: np.ndarray, motion: str, frame: int, frames: int) -> np.ndarray:
+    """The vertices (float64) of one frame of a procedural mesh sequence: frame 0 of every motion is the mesh as given (the
+    canonical pose), later frames add ``dataset_tree_frame``'s smooth, motion-specific displacement."""
+    t = frame / max(frames - 1, 1)
+    w = uniform(seed, f"{motion}/wave", (3, 3), -1.0, 1.0).astype(np.float64)
+    amp = uniform(seed, f"{motion}/amp", (3,), 0.03, 0.08).astype(np.float64)
+    p = np.asarray(verts, dtype=np.float64)
+    return p + t * amp[None, :] * np.sin(2.0 * np.pi * (p @ w.T) + 0.5)
+
+
+def write_mesh_dataset_tree(root, meshes: dict, motions, frames, mesh_file="mesh_norm.ply", data_type="deform4d", seed=0,
+                            held_out_motions=1, norm_params_file="orig_to_gaps.txt", orig2world=None):
+    """``write_dataset_tree``'s directory layout and split lists with one MESH per frame instead of the sample files:
+
+        root/dataset/<sequence>/<frame %04d>/{mesh_file, norm_params_file}
+
+    ``meshes``: identity -> (verts (V, 3), faces (F, 3)), the canonical pose; the frames are ``mesh_tree_vertices``'.  The files
+    hold fp32 vertices; ``orig2world`` (4, 4; default the identity) is written as norm_params_file and the vertices are stored
+    in ORIGINAL coordinates (world = orig2world applied to them) unless "norm" is in ``mesh_file``.  Returns the ``data``
+    section of a config that reads the tree through nsdp_amd.meshstore."""
+    import os
+    from .meshio import write_mesh
+    identities, motions = [str(i) for i in meshes], [str(m) for m in motions]
+    sep = {"deform4d": "_", "deformtransfer": "-"}.get(data_type)
+    if sep is None:
+        raise ValueError(f"write_mesh_dataset_tree: data_type '{data_type}' is neither 'deform4d' nor 'deformtransfer'")
+    for name in identities + motions:
+        if "_" in name or "-" in name or not name:
+            raise ValueError(f"write_mesh_dataset_tree: the name '{name}' must be non-empty and free of '_' and '-'")
+    o2w = np.eye(4) if orig2world is None else np.asarray(orig2world, dtype=np.float64).reshape(4, 4)
+    w2o = np.linalg.inv(o2w)
+    dataset_dir, split_dir = os.path.join(root, "dataset"), os.path.join(root, "splits")
+    for iden in identities:
+        verts, faces = meshes[iden]
+        for motion in motions:
+            for f in range(int(frames)):
+                d = os.path.join(dataset_dir, iden + sep + motion, "%04d" % f)
+                os.makedirs(d, exist_ok=True)
+                v = mesh_tree_vertices(seed, verts, motion, f, int(frames))
+                if "norm" not in mesh_file:
+                    v = (w2o[:3, :3] @ v.T + w2o[:3, 3:4]).T
+                write_mesh(os.path.join(d, mesh_file), v.astype(np.float32), faces)
+                np.savetxt(os.path.join(d, norm_params_file), o2w)
+    os.makedirs(os.path.join(split_dir, data_type), exist_ok=True)
+    held = motions[len(motions) - int(held_out_motions):] if 0 < int(held_out_motions) < len(motions) else []
+    lists = {"identity_seen": [i + sep + motions[0] for i in identities],
+             "train_seen": [i + sep + m for i in identities for m in motions if m not in held],
+             "test_unseen_motions": [i + sep + m for i in identities for m in (held or motions)]}
+    for name, seqs in lists.items():
+        with open(os.path.join(split_dir, data_type, name + ".lst"), "w") as f:
+            f.write("\n".join(seqs) + "\n")
+    return {"type": data_type, "dataset_dir": dataset_dir, "split_dir": split_dir, "interval": 1, "arbitrary": False,
+            "inverse": False, "fix_coord_system": False, "num_surf_samples": 256, "num_space_samples": 128,
+            "partial_range": 0.1, "noise_level": 0.0, "partial_shape_ratio": 1.0, "norm_params_file": norm_params_file,
+            "mesh_file": mesh_file, "space_sigma": [0.1, 0.02]}

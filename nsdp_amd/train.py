@@ -4,11 +4,15 @@ tracking are the reference's; the model, its train/validate functions and the op
 ``nsdp_amd.model``.  The data loader is whatever yields the reference's ``data_dict`` batches: ``--dataset`` trains from the
 data set on disk that ``config["data"]`` names (nsdp_amd.datastore: the reference's directory layout and pair rules, every
 frame resident on the device, the splits and batch sizes of the config's ``training`` / ``validation`` sections as in the
-reference's train.py:105-135); ``--synthetic`` (the default) uses procedural batches.  Not read from disk: the user-handle data
-sets (``tosca``, ``dogrec``), meshes (``load_mesh``), partial shapes, and a data set larger than the device's memory.
+reference's train.py:105-135); ``--mesh-dataset`` trains from the MESH sequences of the same layout (nsdp_amd.meshstore:
+``data["mesh_file"]`` of every frame resident on the device, surface and space rows sampled afresh inside every batch's launch:
+no pre-sampled point files); ``--synthetic`` (the default) uses procedural batches.  Not read from disk: the user-handle data
+sets (``tosca``, ``dogrec``), ``load_mesh`` batches (whole meshes beside the samples), partial shapes, and a data set larger
+than the device's memory.
 
     python -m nsdp_amd.train config.yaml experiment_dir [--synthetic 4] [--epochs 2]
     python -m nsdp_amd.train config.yaml experiment_dir --dataset [--graph] [--gpus N]
+    python -m nsdp_amd.train config.yaml experiment_dir --mesh-dataset [--graph] [--gpus N]
 """
 from __future__ import annotations
 
@@ -199,6 +203,12 @@ def main(argv=None):
                          "deform4d / deformtransfer): splits, num_sampled_pairs and batch_size come from its training / validation "
                          "sections; every frame is held on the device (each rank holds all of them).  Not with --synthetic; "
                          "--batch, --surface, --queries and --uncorresponded describe procedural batches and are not used")
+    ap.add_argument("--mesh-dataset", dest="mesh_dataset", action="store_true",
+                    help="train from the mesh sequences that the config's data section names (as --dataset, with data.mesh_file "
+                         "in every frame directory instead of the pre-sampled point files): every frame's vertices are held on "
+                         "the device and num_surf_samples / num_space_samples rows are sampled afresh for every batch "
+                         "(data.space_sigma: the two offsets of the space rows, default [0.1, 0.02]).  Not with --dataset or "
+                         "--synthetic")
     ap.add_argument("--batch", type=int, default=8, help="shapes per batch = per GPU and step (the global batch is this x --gpus)")
     ap.add_argument("--surface", type=int, default=2048, help="surface samples per shape of the procedural batches (default 2048)")
     ap.add_argument("--queries", type=int, default=8192, help="query points per shape of the procedural batches (default 8192)")
@@ -217,6 +227,10 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.dataset and args.synthetic is not None:
         sys.exit(f"nsdp_amd.train: --dataset and --synthetic {args.synthetic} were given together; choose one source of batches")
+    if args.mesh_dataset and args.dataset:
+        sys.exit("nsdp_amd.train: --mesh-dataset and --dataset were given together; choose one source of batches")
+    if args.mesh_dataset and args.synthetic is not None:
+        sys.exit(f"nsdp_amd.train: --mesh-dataset and --synthetic {args.synthetic} were given together; choose one source of batches")
     if args.synthetic is None:
         args.synthetic = 4
     if args.surface < 1 or args.queries < 1:
@@ -267,6 +281,8 @@ def main(argv=None):
         train_fn = GraphedTrainOnBatch(train_fn, reducer=dp.reducer if dp is not None else None)
     if args.dataset:
         train, val = dataset_loaders(config, args.seed, device, log=say)
+    elif args.mesh_dataset:
+        train, val = mesh_dataset_loaders(config, args.seed, device, log=say)
     else:
         train, val = synthetic_loaders(args, world)
     fit(model, (train_fn, val_fn), lr_scheduler, optimizer, train, val, config, args.experiment_directory, args, device,
@@ -292,6 +308,22 @@ def dataset_loaders(config, seed, device, log=print):
                             device=device, load_mesh=sec.get("load_mesh", False))
         log("Loaded {} {} deformation pairs ({} frames, {:.1f} MB on the device)".format(len(store), what, len(store.frames),
                                                                                       store.nbytes / 1e6))
+        loaders.append(store.loader(sec.get("batch_size", default_batch), seed if section == "training" else seed + 10000,
+                                    noise_generator=None, shuffle=section == "training"))
+    return tuple(loaders)
+
+
+def mesh_dataset_loaders(config, seed, device, log=print):
+    """``dataset_loaders`` over device-resident MESH stores (nsdp_amd.meshstore): (train loader, validation loader) with the same
+    splits, batch sizes, seeds and shuffling; every rank builds both stores whole and takes its share of the batches."""
+    from .meshstore import MeshStore
+    loaders = []
+    for section, default_batch, what in (("training", 16, "training"), ("validation", 1, "validation")):
+        sec = config[section]
+        store = MeshStore(config, sec["iden_split"], sec["motion_split"], num_sampled_pairs=sec.get("num_sampled_pairs", -1),
+                          device=device, load_mesh=sec.get("load_mesh", False))
+        log("Loaded {} {} deformation pairs ({} mesh frames, {:.2f} MB on the device)".format(len(store), what, len(store.frames),
+                                                                                           store.nbytes / 1e6))
         loaders.append(store.loader(sec.get("batch_size", default_batch), seed if section == "training" else seed + 10000,
                                     noise_generator=None, shuffle=section == "training"))
     return tuple(loaders)
