@@ -20,6 +20,7 @@
 #include <climits>
 
 #include "../../include/nsdp_batch.h"
+#include "batch_rows.h"
 #include "common.h"
 #include "draw_key.h"
 #include "prof.h"
@@ -33,6 +34,8 @@ constexpr int kRounds = 8;
 
 using nsdp::absorb;      // (draw_key.h: shared with the other keyed draw)
 using nsdp::mix32;
+using nsdp::aligned;     // (batch_rows.h: shared with the other writer of batch rows)
+using nsdp::clampll;
 
 // `base`: the key after seed, epoch and step (host); rows_out[b, j] = pi_b(j mod n)
 __global__ __launch_bounds__(kThreads) void subset_draw_kernel(const int32_t *__restrict__ n_full, int n_keep, uint32_t base,
@@ -66,10 +69,8 @@ __global__ __launch_bounds__(kThreads) void subset_draw_kernel(const int32_t *__
 struct FrameRef {
   long long surf_first, space_first;
   int surf_rows, space_rows;
-  float min_y, min_z, max_y;
+  nsdp::CanoBox box;
 };
-
-__device__ __forceinline__ long long clampll(long long v, long long lo, long long hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 // the table entry of frame `id` (clamped), its counts and first records clamped to the arenas
 __device__ __forceinline__ FrameRef frame_ref(const int64_t *__restrict__ table, int n_frames, int id, long long surface_rows,
@@ -81,9 +82,7 @@ __device__ __forceinline__ FrameRef frame_ref(const int64_t *__restrict__ table,
   f.space_rows = static_cast<int>(clampll(static_cast<int32_t>(w2 >> 32), 0, min(space_rows, static_cast<long long>(INT_MAX))));
   f.surf_first = clampll(w0, 0, surface_rows - f.surf_rows);
   f.space_first = clampll(w1, 0, space_rows - f.space_rows);
-  f.min_y = __uint_as_float(static_cast<uint32_t>(static_cast<uint64_t>(w3) >> 32));
-  f.min_z = __uint_as_float(static_cast<uint32_t>(static_cast<uint64_t>(w4) & 0xFFFFFFFFu));
-  f.max_y = __uint_as_float(static_cast<uint32_t>(static_cast<uint64_t>(w5) & 0xFFFFFFFFu));
+  f.box = nsdp::cano_box(w3, w4, w5);
   return f;
 }
 
@@ -135,11 +134,8 @@ struct AssembleArgs {
   long long surface_rows, space_rows;
   const int64_t *frame_table;
   const int32_t *frame_ids, *surf_idx, *space_idx;
-  const float *noise;
-  float *surface_out, *inputs_out, *space_out;
-  uint8_t *handle_out;
+  nsdp::RowArgs rows;
   int n_frames, B, n, m, surf_blocks;      // blocks [0, surf_blocks) of the grid's x own surface rows, the others space rows
-  float partial_range, noise_level;
 };
 
 template <bool kSurfF16, bool kSpaceF16>
@@ -157,35 +153,7 @@ __global__ __launch_bounds__(kThreads) void batch_assemble_kernel(const Assemble
     const Rec6 c = load_surface<kSurfF16>(a.surface_arena, record_of(fc.surf_first, fc.surf_rows, idx, a.surface_rows));
     Rec6 s = load_surface<kSurfF16>(a.surface_arena, record_of(fs.surf_first, fs.surf_rows, idx, a.surface_rows));
     const Rec6 t = load_surface<kSurfF16>(a.surface_arena, record_of(ft.surf_first, ft.surf_rows, idx, a.surface_rows));
-    if (a.noise) {
-      const float *z = a.noise + row * 3;
-#pragma unroll
-      for (int k = 0; k < 3; ++k) s.v[k] = __fadd_rn(s.v[k], __fmul_rn(a.noise_level, z[k]));
-    }
-    const bool head = c.v[1] < __fadd_rn(fc.min_y, a.partial_range);
-    const bool tail = c.v[1] > __fsub_rn(fc.max_y, a.partial_range);
-    const bool foot = c.v[2] < __fadd_rn(fc.min_z, a.partial_range);
-    const bool handle = head | tail | foot;
-    const float mf = handle ? 1.f : 0.f;
-    const size_t plane = static_cast<size_t>(a.B) * a.n * 3;
-    float *o = a.surface_out + row * 3;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      o[k] = c.v[k];
-      o[plane + k] = s.v[k];
-      o[2 * plane + k] = t.v[k];
-      o[3 * plane + k] = c.v[3 + k];
-      o[4 * plane + k] = s.v[3 + k];
-      o[5 * plane + k] = t.v[3 + k];
-    }
-    a.handle_out[row] = handle ? 1 : 0;
-    float *in = a.inputs_out + row * 7;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      in[k] = s.v[k];
-      in[3 + k] = __fmul_rn(t.v[k], mf);
-    }
-    in[6] = mf;
+    nsdp::write_surface_row(a.rows, a.B, a.n, row, fc.box, c.v, c.v + 3, s.v, s.v + 3, t.v, t.v + 3);
   } else {
     const int j = (static_cast<int>(blockIdx.x) - a.surf_blocks) * kThreads + static_cast<int>(threadIdx.x);
     if (j >= a.m) return;
@@ -197,18 +165,9 @@ __global__ __launch_bounds__(kThreads) void batch_assemble_kernel(const Assemble
     const Rec3 c = load_space<kSpaceF16>(a.space_arena, record_of(fc.space_first, fc.space_rows, idx, a.space_rows));
     const Rec3 s = load_space<kSpaceF16>(a.space_arena, record_of(fs.space_first, fs.space_rows, idx, a.space_rows));
     const Rec3 t = load_space<kSpaceF16>(a.space_arena, record_of(ft.space_first, ft.space_rows, idx, a.space_rows));
-    const size_t plane = static_cast<size_t>(a.B) * a.m * 3;
-    float *o = a.space_out + row * 3;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      o[k] = c.v[k];
-      o[plane + k] = s.v[k];
-      o[2 * plane + k] = t.v[k];
-    }
+    nsdp::write_space_row(a.rows, a.B, a.m, row, c.v, s.v, t.v);
   }
 }
-
-bool aligned(const void *p, size_t to) { return reinterpret_cast<uintptr_t>(p) % to == 0; }
 
 }  // namespace
 
@@ -233,31 +192,24 @@ extern "C" int nsdp_batch_assemble(const void *surface_arena, long long surface_
                                    const int32_t *frame_ids, int B, const int32_t *surf_idx, int n, const int32_t *space_idx, int m,
                                    float partial_range, const float *noise, float noise_level, float *surface_out,
                                    uint8_t *handle_out, float *inputs_out, float *space_out, void *stream) {
-  NSDP_REQUIRE(B >= 0 && B <= 65535, "batch_assemble: batch B=%d outside [0, 65535]", B);
-  NSDP_REQUIRE(n >= 0 && n <= NSDP_BATCH_MAX_ROWS, "batch_assemble: n=%d surface rows outside [0, %d]", n, NSDP_BATCH_MAX_ROWS);
-  NSDP_REQUIRE(m >= 0 && m <= NSDP_BATCH_MAX_ROWS, "batch_assemble: m=%d space rows outside [0, %d]", m, NSDP_BATCH_MAX_ROWS);
-  NSDP_REQUIRE(static_cast<long long>(B) * (n > m ? n : m) < (1LL << 27), "batch_assemble: B=%d x max(n=%d, m=%d) rows too large", B, n, m);
-  NSDP_REQUIRE(n_frames >= 1, "batch_assemble: n_frames=%d, the frame table needs a frame", n_frames);
+  AssembleArgs a;
+  a.rows = {noise, surface_out, inputs_out, space_out, handle_out, partial_range, noise_level};
+  if (const int rc = nsdp::batch_sizes_ok("batch_assemble", B, n, m, n_frames)) return rc;
   NSDP_REQUIRE(n == 0 || surface_rows >= 1, "batch_assemble: surface_rows=%lld, the surface arena needs a record", surface_rows);
   NSDP_REQUIRE(m == 0 || space_rows >= 1, "batch_assemble: space_rows=%lld, the space arena needs a record", space_rows);
-  NSDP_REQUIRE(nsdp::finite_weight(partial_range), "batch_assemble: partial_range is not finite");
-  NSDP_REQUIRE(nsdp::finite_weight(noise_level), "batch_assemble: noise_level is not finite");
+  if (const int rc = nsdp::batch_values_ok("batch_assemble", a.rows)) return rc;
   if (B == 0 || (n == 0 && m == 0)) return 0;
   NSDP_REQUIRE(frame_table && frame_ids, "batch_assemble: null pointer (frame table / frame ids)");
-  NSDP_REQUIRE(n == 0 || (surface_arena && surf_idx && surface_out && handle_out && inputs_out), "batch_assemble: null pointer (surface operands)");
+  NSDP_REQUIRE(n == 0 || (surface_arena && surf_idx && nsdp::surface_outputs_given(a.rows)), "batch_assemble: null pointer (surface operands)");
   NSDP_REQUIRE(m == 0 || (space_arena && space_out), "batch_assemble: null pointer (space operands)");
   NSDP_REQUIRE((n == 0 || aligned(surface_arena, 16)) && (m == 0 || aligned(space_arena, 16)), "batch_assemble: an arena is not 16-byte aligned");
   NSDP_REQUIRE(aligned(frame_table, 8), "batch_assemble: the frame table is not 8-byte aligned");
-  NSDP_REQUIRE(aligned(frame_ids, 4) && aligned(surf_idx, 4) && aligned(space_idx, 4) && aligned(noise, 4) && aligned(surface_out, 4) &&
-                   aligned(inputs_out, 4) && aligned(space_out, 4),
+  NSDP_REQUIRE(aligned(frame_ids, 4) && aligned(surf_idx, 4) && aligned(space_idx, 4) && nsdp::rows_aligned(a.rows),
                "batch_assemble: an index or fp32 operand is not 4-byte aligned");
-  AssembleArgs a;
   a.surface_arena = surface_arena, a.space_arena = space_arena;
   a.surface_rows = surface_rows > 0 ? surface_rows : 0, a.space_rows = space_rows > 0 ? space_rows : 0;      // (of a part without rows: unread)
-  a.frame_table = frame_table, a.frame_ids = frame_ids, a.surf_idx = surf_idx, a.space_idx = space_idx, a.noise = noise;
-  a.surface_out = surface_out, a.inputs_out = inputs_out, a.space_out = space_out, a.handle_out = handle_out;
+  a.frame_table = frame_table, a.frame_ids = frame_ids, a.surf_idx = surf_idx, a.space_idx = space_idx;
   a.n_frames = n_frames, a.B = B, a.n = n, a.m = m, a.surf_blocks = nsdp::ceil_div(n, kThreads);
-  a.partial_range = partial_range, a.noise_level = noise_level;
   const dim3 grid(a.surf_blocks + nsdp::ceil_div(m, kThreads), B);
   hipStream_t st = nsdp::as_stream(stream);
   NSDP_TRACE("batch_assemble<B=%d,n=%d,m=%d,f16=%d%d>", B, n, m, surface_f16 != 0, space_f16 != 0);

@@ -22,6 +22,7 @@
 
 #include "../../include/nsdp_batch.h"
 #include "../../include/nsdp_meshbatch.h"
+#include "batch_rows.h"
 #include "common.h"
 #include "draw_key.h"
 #include "prof.h"
@@ -34,8 +35,8 @@ constexpr int kThreads = 256;
 
 using nsdp::absorb;      // (draw_key.h: shared with the other keyed draw)
 using nsdp::mix32;
-
-__device__ __forceinline__ long long clampll(long long v, long long lo, long long hi) { return v < lo ? lo : (v > hi ? hi : v); }
+using nsdp::aligned;     // (batch_rows.h: shared with the other writer of batch rows)
+using nsdp::clampll;
 
 struct SampleArgs {
   const float4 *verts;
@@ -44,12 +45,10 @@ struct SampleArgs {
   long long vert_rows, face_rows, thr_rows;
   const int64_t *frame_table, *topo_table;
   const int32_t *frame_ids;
-  const float *noise;
-  float *surface_out, *inputs_out, *space_out;
-  uint8_t *handle_out;
+  nsdp::RowArgs rows;
   int n_frames, n_topos, B, n, m, surf_blocks;      // blocks [0, surf_blocks) of the grid's x own surface rows, the others space rows
   uint32_t base;                                    // the key after seed, epoch and step (host)
-  float partial_range, noise_level, sigma1, sigma2;
+  float sigma1, sigma2;
 };
 
 struct FrameRef {
@@ -143,58 +142,26 @@ __global__ __launch_bounds__(kThreads) void mesh_batch_sample_kernel(const Sampl
   const uint32_t iw = (1u << 24) - iu - iv;
   constexpr float kScale = 1.f / 16777216.f;      // 2^-24: the products are exact
   const float w0 = static_cast<float>(iw) * kScale, u = static_cast<float>(iu) * kScale, v = static_cast<float>(iv) * kScale;
-  Sampled c = sample_triangle(ca, cb, cc, w0, u, v), s = sample_triangle(sa, sb, sc, w0, u, v), t = sample_triangle(ta, tb, tc, w0, u, v);
+  const Sampled c = sample_triangle(ca, cb, cc, w0, u, v), t = sample_triangle(ta, tb, tc, w0, u, v);
+  Sampled s = sample_triangle(sa, sb, sc, w0, u, v);      // (the surface row adds its noise to it)
   if (surface) {
     const size_t row = static_cast<size_t>(b) * a.n + j;
-    if (a.noise) {
-      const float *z = a.noise + row * 3;
-#pragma unroll
-      for (int k = 0; k < 3; ++k) s.p[k] = __fadd_rn(s.p[k], __fmul_rn(a.noise_level, z[k]));
-    }
-    const float min_y = __uint_as_float(static_cast<uint32_t>(static_cast<uint64_t>(ec[3]) >> 32));
-    const float min_z = __uint_as_float(static_cast<uint32_t>(static_cast<uint64_t>(ec[4]) & 0xFFFFFFFFu));
-    const float max_y = __uint_as_float(static_cast<uint32_t>(static_cast<uint64_t>(ec[5]) & 0xFFFFFFFFu));
-    const bool head = c.p[1] < __fadd_rn(min_y, a.partial_range);
-    const bool tail = c.p[1] > __fsub_rn(max_y, a.partial_range);
-    const bool foot = c.p[2] < __fadd_rn(min_z, a.partial_range);
-    const bool handle = head | tail | foot;
-    const float mf = handle ? 1.f : 0.f;
-    const size_t plane = static_cast<size_t>(a.B) * a.n * 3;
-    float *o = a.surface_out + row * 3;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      o[k] = c.p[k];
-      o[plane + k] = s.p[k];
-      o[2 * plane + k] = t.p[k];
-      o[3 * plane + k] = c.nrm[k];
-      o[4 * plane + k] = s.nrm[k];
-      o[5 * plane + k] = t.nrm[k];
-    }
-    a.handle_out[row] = handle ? 1 : 0;
-    float *in = a.inputs_out + row * 7;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      in[k] = s.p[k];
-      in[3 + k] = __fmul_rn(t.p[k], mf);
-    }
-    in[6] = mf;
+    nsdp::write_surface_row(a.rows, a.B, a.n, row, nsdp::cano_box(ec[3], ec[4], ec[5]), c.p, c.nrm, s.p, s.nrm, t.p, t.nrm);
   } else {
     const float t01 = static_cast<float>(word[3] >> 8) * kScale;
     const float tt = __fsub_rn(__fmul_rn(2.f, t01), 1.f);                    // exact: a multiple of 2^-23 in [-1, 1)
     const float d = __fmul_rn(tt, j < a.m / 2 ? a.sigma1 : a.sigma2);
     const size_t row = static_cast<size_t>(b) * a.m + j;
-    const size_t plane = static_cast<size_t>(a.B) * a.m * 3;
-    float *o = a.space_out + row * 3;
+    float cq[3], sq[3], tq[3];
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-      o[k] = __fadd_rn(c.p[k], __fmul_rn(c.nrm[k], d));
-      o[plane + k] = __fadd_rn(s.p[k], __fmul_rn(s.nrm[k], d));
-      o[2 * plane + k] = __fadd_rn(t.p[k], __fmul_rn(t.nrm[k], d));
+      cq[k] = __fadd_rn(c.p[k], __fmul_rn(c.nrm[k], d));
+      sq[k] = __fadd_rn(s.p[k], __fmul_rn(s.nrm[k], d));
+      tq[k] = __fadd_rn(t.p[k], __fmul_rn(t.nrm[k], d));
     }
+    nsdp::write_space_row(a.rows, a.B, a.m, row, cq, sq, tq);
   }
 }
-
-bool aligned(const void *p, size_t to) { return reinterpret_cast<uintptr_t>(p) % to == 0; }
 
 }  // namespace
 
@@ -204,36 +171,30 @@ extern "C" int nsdp_mesh_batch_sample(const float *vert_arena, long long vert_ro
                                       uint64_t seed, uint32_t epoch, uint32_t step, float partial_range, float sigma1, float sigma2,
                                       const float *noise, float noise_level, float *surface_out, uint8_t *handle_out,
                                       float *inputs_out, float *space_out, void *stream) {
-  NSDP_REQUIRE(B >= 0 && B <= 65535, "mesh_batch_sample: batch B=%d outside [0, 65535]", B);
-  NSDP_REQUIRE(n >= 0 && n <= NSDP_BATCH_MAX_ROWS, "mesh_batch_sample: n=%d surface rows outside [0, %d]", n, NSDP_BATCH_MAX_ROWS);
-  NSDP_REQUIRE(m >= 0 && m <= NSDP_BATCH_MAX_ROWS, "mesh_batch_sample: m=%d space rows outside [0, %d]", m, NSDP_BATCH_MAX_ROWS);
-  NSDP_REQUIRE(static_cast<long long>(B) * (n > m ? n : m) < (1LL << 27), "mesh_batch_sample: B=%d x max(n=%d, m=%d) rows too large", B, n, m);
-  NSDP_REQUIRE(n_frames >= 1, "mesh_batch_sample: n_frames=%d, the frame table needs a frame", n_frames);
+  SampleArgs a;
+  a.rows = {noise, surface_out, inputs_out, space_out, handle_out, partial_range, noise_level};
+  if (const int rc = nsdp::batch_sizes_ok("mesh_batch_sample", B, n, m, n_frames)) return rc;
   NSDP_REQUIRE(n_topos >= 1, "mesh_batch_sample: n_topos=%d, the topology table needs a topology", n_topos);
   NSDP_REQUIRE(vert_rows >= 1, "mesh_batch_sample: vert_rows=%lld, the vertex arena needs a record", vert_rows);
   NSDP_REQUIRE(face_rows >= 1, "mesh_batch_sample: face_rows=%lld, the face arena needs a record", face_rows);
   NSDP_REQUIRE(thr_rows >= 1, "mesh_batch_sample: thr_rows=%lld, the threshold arena needs a row", thr_rows);
-  NSDP_REQUIRE(nsdp::finite_weight(partial_range), "mesh_batch_sample: partial_range is not finite");
-  NSDP_REQUIRE(nsdp::finite_weight(noise_level), "mesh_batch_sample: noise_level is not finite");
+  if (const int rc = nsdp::batch_values_ok("mesh_batch_sample", a.rows)) return rc;
   NSDP_REQUIRE(nsdp::finite_weight(sigma1) && nsdp::finite_weight(sigma2), "mesh_batch_sample: sigma1 / sigma2 is not finite");
   if (B == 0 || (n == 0 && m == 0)) return 0;
   NSDP_REQUIRE(vert_arena && face_arena && thr_arena, "mesh_batch_sample: null pointer (arenas)");
   NSDP_REQUIRE(frame_table && topo_table && frame_ids, "mesh_batch_sample: null pointer (tables / frame ids)");
-  NSDP_REQUIRE(n == 0 || (surface_out && handle_out && inputs_out), "mesh_batch_sample: null pointer (surface outputs)");
+  NSDP_REQUIRE(n == 0 || nsdp::surface_outputs_given(a.rows), "mesh_batch_sample: null pointer (surface outputs)");
   NSDP_REQUIRE(m == 0 || space_out, "mesh_batch_sample: null pointer (space output)");
   NSDP_REQUIRE(aligned(vert_arena, 16) && aligned(face_arena, 16), "mesh_batch_sample: an arena is not 16-byte aligned");
   NSDP_REQUIRE(aligned(frame_table, 8) && aligned(topo_table, 8), "mesh_batch_sample: a table is not 8-byte aligned");
-  NSDP_REQUIRE(aligned(thr_arena, 4) && aligned(frame_ids, 4) && aligned(noise, 4) && aligned(surface_out, 4) && aligned(inputs_out, 4) &&
-                   aligned(space_out, 4),
+  NSDP_REQUIRE(aligned(thr_arena, 4) && aligned(frame_ids, 4) && nsdp::rows_aligned(a.rows),
                "mesh_batch_sample: a threshold, index or fp32 operand is not 4-byte aligned");
-  SampleArgs a;
   a.verts = reinterpret_cast<const float4 *>(vert_arena), a.faces = reinterpret_cast<const int4 *>(face_arena), a.thr = thr_arena;
   a.vert_rows = vert_rows, a.face_rows = face_rows, a.thr_rows = thr_rows;
-  a.frame_table = frame_table, a.topo_table = topo_table, a.frame_ids = frame_ids, a.noise = noise;
-  a.surface_out = surface_out, a.inputs_out = inputs_out, a.space_out = space_out, a.handle_out = handle_out;
+  a.frame_table = frame_table, a.topo_table = topo_table, a.frame_ids = frame_ids;
   a.n_frames = n_frames, a.n_topos = n_topos, a.B = B, a.n = n, a.m = m, a.surf_blocks = nsdp::ceil_div(n, kThreads);
   a.base = nsdp::draw_base_key(seed, epoch, step);
-  a.partial_range = partial_range, a.noise_level = noise_level, a.sigma1 = sigma1, a.sigma2 = sigma2;
+  a.sigma1 = sigma1, a.sigma2 = sigma2;
   const dim3 grid(a.surf_blocks + nsdp::ceil_div(m, kThreads), B);
   NSDP_TRACE("mesh_batch_sample<B=%d,n=%d,m=%d>", B, n, m);
   hipLaunchKernelGGL(mesh_batch_sample_kernel, grid, dim3(kThreads), 0, nsdp::as_stream(stream), a);

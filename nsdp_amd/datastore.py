@@ -11,7 +11,8 @@ needs (:209, "before sub-sampling"), so a batch needs no reduction.  A batch is 
 counts of a whole epoch go up in one copy.
 
 Every rank of a data-parallel job holds the WHOLE store (each rank's loader takes its share of the batches, ``shard``); a store
-larger than its byte budget is refused, by name, before anything is allocated on the device.
+larger than its byte budget is refused, by name, before anything is allocated on the device.  What does not depend on a frame
+being a sample pool is ``PairStore``, the core that ``meshstore.MeshStore`` derives from as well.
 
 Out of scope, refused by name: the user-handle data sets (``tosca``, ``dogrec``) and ``load_mesh`` (they need meshes),
 ``partial_shape_ratio < 1`` (the reference's own call site cannot run, see dataset.py), stores larger than device memory.
@@ -41,10 +42,10 @@ class DataStoreError(ValueError):
 
 
 # ---------------------------------------------------------------------------------------------------------------- pair rules
-def _read_split(cfg_data, split):
+def _read_split(cfg_data, split, refuse):
     path = os.path.join(cfg_data["split_dir"], cfg_data["type"], split + ".lst")
     if not os.path.isfile(path):
-        raise DataStoreError(f"SampleStore: missing split list {path}")
+        refuse(f"missing split list {path}")
     with open(path) as f:
         return f.read().split("\n")
 
@@ -58,19 +59,21 @@ def _is_seq(cfg_data, name):
     return name != "" and os.path.isdir(os.path.join(cfg_data["dataset_dir"], name))
 
 
-def form_pairs(cfg_data: dict, iden_split: str, motion_split: str) -> list:
+def form_pairs(cfg_data: dict, iden_split: str, motion_split: str, refuse=None) -> list:
     """``all_deform_pairs`` before any shuffle, as the reference's ``_load`` forms them: a list of ``pair_info`` tuples
     (idx_cano, cano sequence, cano frame, idx_motion, source sequence, source frame, target sequence, target frame).
     ``deform4d``: dataset_deform4d_flow.py:37-117; ``deformtransfer``: dataset_deformtransfer_flow.py:38-116 (no identity list:
-    a sequence is its own canonical sequence; ``arbitrary`` has the evaluation rule only, with the per-animal source frame)."""
+    a sequence is its own canonical sequence; ``arbitrary`` has the evaluation rule only, with the per-animal source frame).
+    ``refuse``: the store's refusal, for a missing split list (default: ``SampleStore``'s)."""
+    refuse = refuse or SampleStore._refuse
     kind = cfg_data["type"]
     train = motion_split[:5] == "train"
-    motion_names = _read_split(cfg_data, motion_split)
+    motion_names = _read_split(cfg_data, motion_split, refuse)
     motion_dirs = sorted(n for n in motion_names if _is_seq(cfg_data, n))       # (sorting the joined paths sorts the names)
     motion_index = {n: i for i, n in enumerate(motion_dirs)}
     cano_of = {}
     if kind == "deform4d":
-        iden_dirs = sorted(n for n in _read_split(cfg_data, iden_split) if _is_seq(cfg_data, n))
+        iden_dirs = sorted(n for n in _read_split(cfg_data, iden_split, refuse) if _is_seq(cfg_data, n))
         for i, seq in enumerate(iden_dirs):
             cano_of[seq.split("_")[0]] = (i, seq)                                # (a later sequence of one identity wins, as there)
     pairs = []
@@ -165,6 +168,27 @@ def _arena_ptr(t, name):
     return ctypes.c_void_p(t.data_ptr())
 
 
+def _batch_outputs(B, n, m, device):
+    """What a batch launch writes, in the order both entries take the pointers (``_ptrs``): surface [6, B, n, 3], handle
+    [B, n, 1] (bytes), inputs [B, n, 7], space [3, B, m, 3]."""
+    f32 = dict(dtype=torch.float32, device=device)
+    return (torch.empty((6, B, n, 3), **f32), torch.empty((B, n, 1), dtype=torch.uint8, device=device),
+            torch.empty((B, n, 7), **f32), torch.empty((3, B, m, 3), **f32))
+
+
+def _ptrs(tensors):
+    return [ctypes.c_void_p(t.data_ptr()) for t in tensors]
+
+
+def _data_dict(surface, handle, inputs, space) -> dict:
+    """The data_dict of ``dataset.prepare_batch`` as views of ``_batch_outputs``' tensors."""
+    out = dict(zip((f"{key}_{name}" for key in ("surface_samples", "surface_normals") for name in _KEYS), surface))      # six planes
+    out["cano_handle_sample_idx"] = handle.view(torch.bool)
+    out["surface_samples_inputs"] = inputs
+    out.update(zip((f"space_samples_{name}" for name in _KEYS), space))
+    return out
+
+
 def batch_assemble(surface_arena, space_arena, frame_table, frame_ids, surf_idx, space_idx, m, partial_range, noise=None,
                    noise_level=0.0) -> dict:
     """nsdp_batch_assemble: the arenas (rows, 6) / (rows, 4) fp16 or fp32, frame_table (F, 6) int64, frame_ids (3, B) int32
@@ -178,10 +202,7 @@ def batch_assemble(surface_arena, space_arena, frame_table, frame_ids, surf_idx,
         raise NsdpHipError(f"noise must be [B, n, 3] = {(B, n, 3)}, got {tuple(noise.shape)}")
     if space_idx is not None:
         m = space_idx.shape[1]
-    surface = torch.empty((6, B, n, 3), dtype=torch.float32, device=dev)
-    handle = torch.empty((B, n, 1), dtype=torch.uint8, device=dev)
-    inputs = torch.empty((B, n, 7), dtype=torch.float32, device=dev)
-    space = torch.empty((3, B, int(m), 3), dtype=torch.float32, device=dev)
+    outputs = _batch_outputs(B, n, int(m), dev)
     with on_device(surf_idx):
         check(lib().nsdp_batch_assemble(
             _arena_ptr(surface_arena, "surface_arena"), ctypes.c_longlong(surface_arena.shape[0]),
@@ -190,17 +211,8 @@ def batch_assemble(surface_arena, space_arena, frame_table, frame_ids, surf_idx,
             ctypes.c_void_p(frame_table.data_ptr()), ctypes.c_int(frame_table.shape[0]), iptr(frame_ids, "frame_ids"), ctypes.c_int(B),
             iptr(surf_idx, "surf_idx"), ctypes.c_int(n), optptr(None) if space_idx is None else iptr(space_idx, "space_idx"),
             ctypes.c_int(int(m)), ctypes.c_float(partial_range), optptr(None) if noise is None else ctypes.c_void_p(_f32(noise).data_ptr()),
-            ctypes.c_float(noise_level), ctypes.c_void_p(surface.data_ptr()), ctypes.c_void_p(handle.data_ptr()),
-            ctypes.c_void_p(inputs.data_ptr()), ctypes.c_void_p(space.data_ptr()), stream_ptr()), "nsdp_batch_assemble")
-    out = {}
-    for k, key in enumerate(("surface_samples", "surface_normals")):
-        for i, name in enumerate(_KEYS):
-            out[f"{key}_{name}"] = surface[3 * k + i]
-    out["cano_handle_sample_idx"] = handle.view(torch.bool)
-    out["surface_samples_inputs"] = inputs
-    for i, name in enumerate(_KEYS):
-        out[f"space_samples_{name}"] = space[i]
-    return out
+            ctypes.c_float(noise_level), *_ptrs(outputs), stream_ptr()), "nsdp_batch_assemble")
+    return _data_dict(*outputs)
 
 
 def _f32(t):
@@ -210,43 +222,49 @@ def _f32(t):
 
 
 # ---------------------------------------------------------------------------------------------------------------- the store
-class SampleStore:
-    """The frames of ``config["data"]`` that the pairs of (iden_split, motion_split) reference, on ``device``.
+class PairStore:
+    """A device-resident store of the (canonical, source, target) frames that the pairs of (iden_split, motion_split) of
+    ``config["data"]`` reference, whatever a frame holds: ``SampleStore`` (sample pools) and ``meshstore.MeshStore`` (meshes)
+    add what a frame IS, and for ``StoreLoader`` a ``batch(plan, seed, epoch, step, noise)`` of a slice of ``plan_rows``.
 
     ``pairs``: the pair_info tuples in the reference's ``all_deform_pairs`` order before its first shuffle; ``sample_indices(e)``:
     the positions (into ``pairs``) of ``sample_deform_pairs`` during epoch ``e`` -- the reference reshuffles when the last index of
-    a train split is fetched, here that happens at the end of each epoch.  Each rank of a data-parallel job holds the whole store.
-    ``byte_budget``: the most device memory the arenas may take (default: half of the device's memory)."""
+    a train split is fetched, here that happens at the end of each epoch.  Each rank of a data-parallel job holds the whole store."""
 
-    def __init__(self, config, iden_split, motion_split, num_sampled_pairs=-1, device="cuda", load_mesh=False, byte_budget=None,
-                 pairs_only=False):
+    _error = DataStoreError
+    # why THIS store cannot serve what every store refuses by name: the user-handle data sets, load_mesh, partial shapes
+    _refused = (None, None, None)
+
+    def __init__(self, config, iden_split, motion_split, num_sampled_pairs, load_mesh):
         data = config["data"]
         self.cfg_data, self.iden_split, self.motion_split = data, iden_split, motion_split
         self.num_sampled_pairs = int(num_sampled_pairs)
         self.is_train = motion_split[:5] == "train"
         kind = data.get("type")
+        no_handles, no_load_mesh, no_partial = self._refused
         if kind in ("tosca", "dogrec"):
-            raise DataStoreError(f"SampleStore: data type '{kind}' (the user-handle data sets) needs meshes and is not supported")
+            self._refuse(f"data type '{kind}' (the user-handle data sets) {no_handles}")
         if kind not in ("deform4d", "deformtransfer"):
-            raise DataStoreError(f"SampleStore: unknown data type '{kind}' (deform4d and deformtransfer are read)")
+            self._refuse(f"unknown data type '{kind}' (deform4d and deformtransfer are read)")
         if load_mesh:
-            raise DataStoreError("SampleStore: load_mesh is not supported (meshes are not read from a data set)")
+            self._refuse(no_load_mesh)
         if data.get("partial_shape_ratio", 1.0) < 1.0:
-            raise DataStoreError("SampleStore: partial_shape_ratio < 1 is not supported from disk (the reference's own call site "
-                                 "cannot run, see nsdp_amd/dataset.py)")
+            self._refuse(no_partial)
         if not os.path.isdir(data["dataset_dir"]):
-            raise DataStoreError(f"SampleStore: missing dataset_dir {data['dataset_dir']}")
-        self.pairs = form_pairs(data, iden_split, motion_split)
+            self._refuse(f"missing dataset_dir {data['dataset_dir']}")
+        self.pairs = form_pairs(data, iden_split, motion_split, self._refuse)
         if not self.pairs:
-            raise DataStoreError(f"SampleStore: the splits '{iden_split}' / '{motion_split}' form no deformation pair")
+            self._refuse(f"the splits '{iden_split}' / '{motion_split}' form no deformation pair")
         self._orders = []                 # _orders[k]: `all_deform_pairs` as positions into self.pairs after k + 1 shuffles
         self.n = int(data["num_surf_samples"])
-        if pairs_only:
-            return
-        self.device = torch.device(device)
-        self._index_frames()
-        self._judge(byte_budget)
-        self._load()
+
+    @classmethod
+    def _refuse(cls, text):
+        raise cls._error(f"{cls.__name__}: {text}")
+
+    def _need_gpu(self):
+        if self.device.type != "cuda":
+            raise NsdpHipError(f"{type(self).__name__} needs a GPU device (CPU not supported, no fallback)")
 
     # -------------------------------------------------------------------------------------------------------- sample lists
     def sample_indices(self, epoch: int = 0) -> list:
@@ -288,6 +306,58 @@ class SampleStore:
     def _workers(self):
         return max(1, min(16, cpu_budget.cpu_budget()))
 
+    def frame_bbox(self, frame_id):
+        """(bbox_min, bbox_max) float32 of a frame (a pool's full surface cloud, a mesh's vertices), from the host frame table."""
+        box = self.frame_table_host[frame_id, 3:6].copy().view(np.float32)
+        return box[:3], box[3:]
+
+    def _judge_bytes(self, nbytes, byte_budget):
+        """The byte budget (default: half of the device's memory), judged on the host: nothing has been allocated yet."""
+        self.nbytes = int(nbytes)
+        if byte_budget is None:
+            self._need_gpu()
+            byte_budget = torch.cuda.get_device_properties(self.device).total_memory // 2
+        self.byte_budget = int(byte_budget)
+        if self.nbytes > self.byte_budget:
+            self._refuse(f"{len(self.frames)} frames need {self.nbytes} bytes on the device, more than the byte budget of "
+                         f"{self.byte_budget} bytes (a store larger than device memory is not supported)")
+
+    # -------------------------------------------------------------------------------------------------------- batches
+    def plan_rows(self, samples):
+        """An epoch's plan: a column per sample, its (cano, src, tgt) frame ids as the pairs list them (a store may add rows)."""
+        return self.pair_frames[samples].T
+
+    def _oriented(self, frame_ids):
+        """``frame_ids`` (3, B) with ``inverse`` applied, as ``prepare_batch`` applies it: source and target swapped."""
+        data = self.cfg_data
+        return frame_ids[[0, 2, 1]].contiguous() if not data["arbitrary"] and data["inverse"] else frame_ids
+
+    def _noise_of(self, noise):
+        """(the noise tensor a launch gets, noise_level): no tensor unless ``noise_level > 0``, which needs one."""
+        level = float(self.cfg_data["noise_level"])
+        if level > 0.0 and noise is None:
+            raise self._error(f"{type(self).__name__}.assemble: noise_level > 0 needs a noise tensor")
+        return (noise if level > 0.0 else None), level
+
+
+class SampleStore(PairStore):
+    """The store of PRE-SAMPLED frames: each frame's surface pool (points and normals) and space pool in two packed arenas.
+    ``byte_budget``: the most device memory the arenas may take (default: half of the device's memory)."""
+
+    _refused = ("needs meshes and is not supported", "load_mesh is not supported (meshes are not read from a data set)",
+                "partial_shape_ratio < 1 is not supported from disk (the reference's own call site cannot run, see "
+                "nsdp_amd/dataset.py)")
+
+    def __init__(self, config, iden_split, motion_split, num_sampled_pairs=-1, device="cuda", load_mesh=False, byte_budget=None,
+                 pairs_only=False):
+        super().__init__(config, iden_split, motion_split, num_sampled_pairs, load_mesh)
+        if pairs_only:
+            return
+        self.device = torch.device(device)
+        self._index_frames()
+        self._judge(byte_budget)
+        self._load()
+
     def _judge(self, byte_budget):
         """Everything that is refused, from the files' headers: nothing has been allocated yet."""
         data = self.cfg_data
@@ -314,15 +384,12 @@ class SampleStore:
                                      f"than the {MAX_ROWS} a frame may hold")
             if fr.surf_rows < self.n:
                 raise DataStoreError(f"SampleStore: frame {fr.dir} has {fr.surf_rows} surface rows, fewer than num_surf_samples = {self.n}")
-        for info, (c, s, t) in zip(self.pairs, self.pair_frames):
-            rows = [self.frames[i].surf_rows for i in (c, s, t)]
-            if len(set(rows)) != 1:
-                raise DataStoreError(f"SampleStore: the frames of pair {info[1]}/{info[2]}, {info[4]}/{info[5]}, {info[6]}/{info[7]} differ "
-                                     f"in surface count ({rows}); the row indices are correspondences")
-            rows = [self.frames[i].space_rows for i in (c, s, t)]
-            if len(set(rows)) != 1:
-                raise DataStoreError(f"SampleStore: the frames of pair {info[1]}/{info[2]}, {info[4]}/{info[5]}, {info[6]}/{info[7]} differ "
-                                     f"in space count ({rows}); the row indices are correspondences")
+        for info, ids in zip(self.pairs, self.pair_frames):
+            for what, attr in (("surface", "surf_rows"), ("space", "space_rows")):
+                rows = [getattr(self.frames[i], attr) for i in ids]
+                if len(set(rows)) != 1:
+                    self._refuse(f"the frames of pair {info[1]}/{info[2]}, {info[4]}/{info[5]}, {info[6]}/{info[7]} differ in {what} "
+                                 f"count ({rows}); the row indices are correspondences")
         want = int(data["num_space_samples"])
         counts = sorted({fr.space_rows for fr in self.frames})
         if counts[0] > want:
@@ -342,20 +409,12 @@ class SampleStore:
         self.space_dtype = torch.float16 if all(fr.space_dtype == f16 for fr in self.frames) else torch.float32
         self.surface_rows = sum(fr.surf_rows for fr in self.frames)
         self.space_rows = sum(fr.space_rows for fr in self.frames)
-        self.nbytes = (self.surface_rows * SURFACE_RECORD * (2 if self.surface_dtype == torch.float16 else 4)
-                       + self.space_rows * SPACE_RECORD * (2 if self.space_dtype == torch.float16 else 4) + 48 * len(self.frames))
-        if byte_budget is None:
-            if self.device.type != "cuda":
-                raise NsdpHipError("SampleStore needs a GPU device (CPU not supported, no fallback)")
-            byte_budget = torch.cuda.get_device_properties(self.device).total_memory // 2
-        self.byte_budget = int(byte_budget)
-        if self.nbytes > self.byte_budget:
-            raise DataStoreError(f"SampleStore: {len(self.frames)} frames need {self.nbytes} bytes on the device, more than the "
-                                 f"byte budget of {self.byte_budget} bytes (a store larger than device memory is not supported)")
+        self._judge_bytes(self.surface_rows * SURFACE_RECORD * (2 if self.surface_dtype == torch.float16 else 4)
+                          + self.space_rows * SPACE_RECORD * (2 if self.space_dtype == torch.float16 else 4) + 48 * len(self.frames),
+                          byte_budget)
 
     def _load(self):
-        if self.device.type != "cuda":
-            raise NsdpHipError("SampleStore needs a GPU device (CPU not supported, no fallback)")
+        self._need_gpu()
         data = self.cfg_data
         fix = bool(data["fix_coord_system"])
         np_surf = np.float16 if self.surface_dtype == torch.float16 else np.float32
@@ -397,11 +456,6 @@ class SampleStore:
         self.space_counts = np.array([fr.space_rows for fr in self.frames], dtype=np.int32)
 
     # -------------------------------------------------------------------------------------------------------- batches
-    def frame_bbox(self, frame_id):
-        """(bbox_min, bbox_max) float32 of a frame's full surface cloud, from the host copy of the frame table."""
-        box = self.frame_table_host[frame_id, 3:6].copy().view(np.float32)
-        return box[:3], box[3:]
-
     def frame_arrays(self, frame_id):
         """A frame's arrays as fp32 device tensors {surface_samples, surface_normals, space_samples} (for tests and tools)."""
         fr = self.frames[frame_id]
@@ -412,14 +466,21 @@ class SampleStore:
     def assemble(self, frame_ids, surf_idx, space_idx=None, noise=None) -> dict:
         """The data_dict of the samples whose (cano, src, tgt) frames are ``frame_ids`` (3, B) int32 on the device, as the pairs
         list them: ``inverse`` is applied here, as ``prepare_batch`` applies it."""
-        data = self.cfg_data
-        if not data["arbitrary"] and data["inverse"]:
-            frame_ids = frame_ids[[0, 2, 1]].contiguous()
-        level = float(data["noise_level"])
-        if level > 0.0 and noise is None:
-            raise DataStoreError("SampleStore.assemble: noise_level > 0 needs a noise tensor")
-        return batch_assemble(self.surface_arena, self.space_arena, self.frame_table, frame_ids, surf_idx, space_idx, self.m,
-                              float(data["partial_range"]), noise if level > 0.0 else None, level)
+        noise, level = self._noise_of(noise)
+        return batch_assemble(self.surface_arena, self.space_arena, self.frame_table, self._oriented(frame_ids), surf_idx, space_idx,
+                              self.m, float(self.cfg_data["partial_range"]), noise, level)
+
+    def plan_rows(self, samples):
+        """The frame ids, and below them the row counts of each sample's surface and space pool: what its draws are taken from."""
+        ids = self.pair_frames[samples]
+        return np.concatenate([ids.T, self.surf_counts[ids[:, 0]][None], self.space_counts[ids[:, 0]][None]], axis=0)
+
+    def batch(self, plan, seed, epoch, step, noise=None) -> dict:
+        """The batch of the samples in ``plan`` (columns of ``plan_rows``, on the device) with nsdp_subset_draw's rows for
+        (seed, epoch, step)."""
+        surf_idx = subset_draw(plan[3].contiguous(), self.n, seed, epoch, step, SURFACE)
+        space_idx = subset_draw(plan[4].contiguous(), self.m, seed, epoch, step, SPACE) if self.draw_space else None
+        return self.assemble(plan[:3].contiguous(), surf_idx, space_idx, noise)
 
     def loader(self, batch, seed, noise_generator=None, shuffle=None):
         return StoreLoader(self, batch, seed, noise_generator, shuffle)
@@ -427,8 +488,9 @@ class SampleStore:
 
 class StoreLoader:
     """An iterable of data_dict batches on the store's device; every pass over it is one epoch (its number counts up from 0).
-    ``shuffle`` (default: train splits) orders an epoch's samples by ``epoch_permutation(seed, epoch)``; the row subsets of batch
-    ``step`` of epoch ``epoch`` are nsdp_subset_draw's for (seed, epoch, step), so two loaders with one seed give equal batches.
+    ``shuffle`` (default: train splits) orders an epoch's samples by ``epoch_permutation(seed, epoch)``; the rows of batch ``step``
+    of epoch ``epoch`` are the store's draw for (seed, epoch, step), so two loaders with one seed give equal batches.  One plan
+    copy per epoch (``store.plan_rows``), then ``store.batch`` per step; nothing is read back.
     The last partial batch of an epoch is yielded as it is.  ``noise_generator``: a torch.Generator on the device for the
     source noise (``noise_level > 0``)."""
 
@@ -453,19 +515,14 @@ class StoreLoader:
         st = self.store
         epoch, self.epoch = self.epoch, self.epoch + 1
         samples = self.epoch_samples(epoch)
-        ids = st.pair_frames[samples]                                                     # (E, 3)
-        plan = np.concatenate([ids.T, st.surf_counts[ids[:, 0]][None], st.space_counts[ids[:, 0]][None]], axis=0)
-        plan = torch.from_numpy(np.ascontiguousarray(plan, dtype=np.int32)).to(st.device, non_blocking=True)      # one copy per epoch
+        plan = torch.from_numpy(np.ascontiguousarray(st.plan_rows(samples), dtype=np.int32)).to(st.device, non_blocking=True)      # one copy per epoch
         level = float(st.cfg_data["noise_level"])
         for step in steps:
             lo, hi = step * self.batch, min((step + 1) * self.batch, len(samples))
-            frame_ids = plan[:3, lo:hi].contiguous()
-            surf_idx = subset_draw(plan[3, lo:hi].contiguous(), st.n, self.seed, epoch, step, SURFACE)
-            space_idx = subset_draw(plan[4, lo:hi].contiguous(), st.m, self.seed, epoch, step, SPACE) if st.draw_space else None
             noise = None
             if level > 0.0:
                 noise = torch.randn((hi - lo, st.n, 3), device=st.device, generator=self.noise_generator)
-            yield st.assemble(frame_ids, surf_idx, space_idx, noise)
+            yield st.batch(plan[:, lo:hi].contiguous(), self.seed, epoch, step, noise)
 
     def __iter__(self):
         return self._batches(range(len(self)))

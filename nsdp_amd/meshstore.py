@@ -35,7 +35,7 @@ import torch
 
 from . import meshio
 from ._lib import NsdpHipError, check, fptr, iptr, lib, on_device, optptr, stream_ptr
-from .datastore import _KEYS, DataStoreError, SampleStore, StoreLoader, _f32, _fix_coord_system, form_pairs      # noqa: F401 (form_pairs: the pair rules, re-exported)
+from .datastore import DataStoreError, PairStore, StoreLoader, _batch_outputs, _data_dict, _f32, _fix_coord_system, _ptrs, form_pairs      # noqa: F401 (form_pairs: the pair rules, re-exported)
 
 MESH_SURFACE, MESH_SPACE = 2, 3        # NSDP_DRAW_MESH_SURFACE / NSDP_DRAW_MESH_SPACE: the `which` of the two draws' keys
 MAX_ELEMS = 1 << 21                    # NSDP_MESH_MAX_ELEMS: vertices of a frame, faces of a topology
@@ -150,10 +150,7 @@ def mesh_batch_sample(vert_arena, face_arena, thr_arena, frame_table, topo_table
             raise NsdpHipError(f"{name} lives on {t.device}, frame_ids on {dev}: one launch reads them all")
     if noise is not None and tuple(noise.shape) != (B, n, 3):
         raise NsdpHipError(f"noise must be [B, n, 3] = {(B, n, 3)}, got {tuple(noise.shape)}")
-    surface = torch.empty((6, B, n, 3), dtype=torch.float32, device=dev)
-    handle = torch.empty((B, n, 1), dtype=torch.uint8, device=dev)
-    inputs = torch.empty((B, n, 7), dtype=torch.float32, device=dev)
-    space = torch.empty((3, B, m, 3), dtype=torch.float32, device=dev)
+    outputs = _batch_outputs(B, n, m, dev)
     with on_device(frame_ids):
         check(lib().nsdp_mesh_batch_sample(
             fptr(vert_arena, "vert_arena"),
@@ -163,57 +160,45 @@ def mesh_batch_sample(vert_arena, face_arena, thr_arena, frame_table, topo_table
             iptr(frame_ids, "frame_ids"), ctypes.c_int(B), ctypes.c_int(n), ctypes.c_int(m),
             ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), ctypes.c_uint32(int(epoch) & 0xFFFFFFFF),
             ctypes.c_uint32(int(step) & 0xFFFFFFFF), ctypes.c_float(partial_range), ctypes.c_float(sigma1), ctypes.c_float(sigma2),
-            optptr(None) if noise is None else ctypes.c_void_p(_f32(noise).data_ptr()), ctypes.c_float(noise_level),
-            ctypes.c_void_p(surface.data_ptr()), ctypes.c_void_p(handle.data_ptr()), ctypes.c_void_p(inputs.data_ptr()),
-            ctypes.c_void_p(space.data_ptr()), stream_ptr()), "nsdp_mesh_batch_sample")
-    out = {}
-    for k, key in enumerate(("surface_samples", "surface_normals")):
-        for i, name in enumerate(_KEYS):
-            out[f"{key}_{name}"] = surface[3 * k + i]
-    out["cano_handle_sample_idx"] = handle.view(torch.bool)
-    out["surface_samples_inputs"] = inputs
-    for i, name in enumerate(_KEYS):
-        out[f"space_samples_{name}"] = space[i]
-    return out
+            optptr(None) if noise is None else ctypes.c_void_p(_f32(noise).data_ptr()), ctypes.c_float(noise_level), *_ptrs(outputs),
+            stream_ptr()), "nsdp_mesh_batch_sample")
+    return _data_dict(*outputs)
 
 
 # ---------------------------------------------------------------------------------------------------------------- the store
-class MeshStore(SampleStore):
-    """The mesh frames of ``config["data"]`` that the pairs of (iden_split, motion_split) reference, on ``device``.  The
-    constructor's arguments, ``pairs``, ``sample_indices``, ``len()`` and ``pairs_only`` are ``SampleStore``'s.  ``nbytes``: what
-    the arenas and tables take on the device; ``byte_budget``: the most they may (default: half of the device's memory)."""
+class MeshStore(PairStore):
+    """The store of MESH frames: every distinct frame's vertices, one face block per topology and the area thresholds of every
+    canonical frame.  The constructor's arguments, ``pairs``, ``sample_indices``, ``len()`` and ``pairs_only`` are as
+    ``SampleStore``'s (both are ``datastore.PairStore``s).  ``nbytes``: what the arenas and tables take on the device;
+    ``byte_budget``: the most they may (default: half of the device's memory)."""
+
+    _error = MeshStoreError
+    _refused = ("is not supported", "load_mesh batches (whole meshes beside the samples) are not supported",
+                "partial_shape_ratio < 1 (partial shapes) is not supported")
 
     def __init__(self, config, iden_split, motion_split, num_sampled_pairs=-1, device="cuda", load_mesh=False, byte_budget=None,
                  pairs_only=False):
-        data = config["data"]
-        kind = data.get("type")
-        # the three refusals whose reasons differ from SampleStore's ...
-        if kind in ("tosca", "dogrec"):
-            raise MeshStoreError(f"MeshStore: data type '{kind}' (the user-handle data sets) is not supported")
-        if load_mesh:
-            raise MeshStoreError("MeshStore: load_mesh batches (whole meshes beside the samples) are not supported")
-        if data.get("partial_shape_ratio", 1.0) < 1.0:
-            raise MeshStoreError("MeshStore: partial_shape_ratio < 1 (partial shapes) is not supported")
-        # ... then SampleStore's own prologue as it stands (known types, dataset_dir, the pairs, the shuffle state), not a copy of it
-        try:
-            SampleStore.__init__(self, config, iden_split, motion_split, num_sampled_pairs, pairs_only=True)
-        except DataStoreError as e:
-            raise MeshStoreError(str(e).replace("SampleStore:", "MeshStore:")) from None
+        super().__init__(config, iden_split, motion_split, num_sampled_pairs, load_mesh)
+        data = self.cfg_data
         self.m = int(data["num_space_samples"])
         if pairs_only:
             return
         if "mesh_file" not in data:
-            raise MeshStoreError("MeshStore: the data section names no mesh_file")
+            self._refuse("the data section names no mesh_file")
         if not 0 <= self.n <= MAX_ROWS or not 0 <= self.m <= MAX_ROWS:
-            raise MeshStoreError(f"MeshStore: num_surf_samples = {self.n} / num_space_samples = {self.m} outside [0, {MAX_ROWS}]")
+            self._refuse(f"num_surf_samples = {self.n} / num_space_samples = {self.m} outside [0, {MAX_ROWS}]")
         sigma = data.get("space_sigma", list(DEFAULT_SIGMA))
         if len(sigma) != 2 or not all(np.isfinite(float(s)) for s in sigma):
-            raise MeshStoreError(f"MeshStore: space_sigma = {sigma} must be two finite numbers")
+            self._refuse(f"space_sigma = {sigma} must be two finite numbers")
         self.sigma = (float(sigma[0]), float(sigma[1]))
         self.device = torch.device(device)
         self._index_frames()
         host = self._read()
-        self._judge_bytes(byte_budget, host)
+        self.vert_rows = sum(v.shape[0] for v in host["verts"])
+        self.face_rows = sum(f.shape[0] for f in host["faces"])
+        self.thr_rows = sum(host["faces"][host["topo_of"][k]].shape[0] for k in host["cano"])
+        self._judge_bytes(16 * self.vert_rows + 16 * self.face_rows + 4 * self.thr_rows + 48 * len(self.frames) + 16 * len(host["faces"]),
+                          byte_budget)
         self._upload(host)
 
     # -------------------------------------------------------------------------------------------------------- frames
@@ -246,24 +231,8 @@ class MeshStore(SampleStore):
                                      f"drawn by area") from None
         return {"verts": verts, "topo_of": topo_of, "faces": faces, "cano": cano, "thresholds": thresholds}
 
-    def _judge_bytes(self, byte_budget, host):
-        """The byte budget, from the host arrays: nothing has been allocated on the device yet."""
-        self.vert_rows = sum(v.shape[0] for v in host["verts"])
-        self.face_rows = sum(f.shape[0] for f in host["faces"])
-        self.thr_rows = sum(host["faces"][host["topo_of"][k]].shape[0] for k in host["cano"])
-        self.nbytes = 16 * self.vert_rows + 16 * self.face_rows + 4 * self.thr_rows + 48 * len(self.frames) + 16 * len(host["faces"])
-        if byte_budget is None:
-            if self.device.type != "cuda":
-                raise NsdpHipError("MeshStore needs a GPU device (CPU not supported, no fallback)")
-            byte_budget = torch.cuda.get_device_properties(self.device).total_memory // 2
-        self.byte_budget = int(byte_budget)
-        if self.nbytes > self.byte_budget:
-            raise MeshStoreError(f"MeshStore: {len(self.frames)} frames need {self.nbytes} bytes on the device, more than the "
-                                 f"byte budget of {self.byte_budget} bytes (a store larger than device memory is not supported)")
-
     def _upload(self, host):
-        if self.device.type != "cuda":
-            raise NsdpHipError("MeshStore needs a GPU device (CPU not supported, no fallback)")
+        self._need_gpu()
         packed = pack(host["verts"], host["topo_of"], host["faces"], host["cano"], host["thresholds"])
         self.topo_of = np.asarray(host["topo_of"], dtype=np.int32)
         self.frame_table_host, self.topo_table_host = packed["frame_table"], packed["topo_table"]
@@ -280,26 +249,15 @@ class MeshStore(SampleStore):
         f0, count = (int(x) for x in self.topo_table_host[word >> 32])
         return (self.vert_arena[first:first + (word & 0xFFFFFFFF), :3].contiguous(), self.face_arena[f0:f0 + count, :3].contiguous())
 
-    def frame_bbox(self, frame_id):
-        """(bbox_min, bbox_max) float32 of a frame's VERTICES, from the host copy of the frame table."""
-        return super().frame_bbox(frame_id)      # (the box sits in the same three words of an entry)
-
-    def frame_arrays(self, frame_id):
-        """``SampleStore``'s view of a frame's sample pools: a mesh store has none, and says so instead of failing on a missing arena."""
-        raise MeshStoreError("MeshStore holds meshes, not sample pools: see mesh(frame_id)")
-
     def assemble(self, frame_ids, seed, epoch, step, noise=None) -> dict:
         """The data_dict of the samples whose (cano, src, tgt) frames are ``frame_ids`` (3, B) int32 on the device, as the pairs
         list them (``inverse`` is applied here, as ``prepare_batch`` applies it), with the rows of (seed, epoch, step)."""
-        data = self.cfg_data
-        if not data["arbitrary"] and data["inverse"]:
-            frame_ids = frame_ids[[0, 2, 1]].contiguous()
-        level = float(data["noise_level"])
-        if level > 0.0 and noise is None:
-            raise MeshStoreError("MeshStore.assemble: noise_level > 0 needs a noise tensor")
-        return mesh_batch_sample(self.vert_arena, self.face_arena, self.thr_arena, self.frame_table, self.topo_table, frame_ids, self.n,
-                                 self.m, seed, epoch, step, float(data["partial_range"]), self.sigma[0], self.sigma[1],
-                                 noise if level > 0.0 else None, level)
+        noise, level = self._noise_of(noise)
+        return mesh_batch_sample(self.vert_arena, self.face_arena, self.thr_arena, self.frame_table, self.topo_table,
+                                 self._oriented(frame_ids), self.n, self.m, seed, epoch, step, float(self.cfg_data["partial_range"]),
+                                 self.sigma[0], self.sigma[1], noise, level)
+
+    batch = assemble      # (a loader's plan is the frame ids alone: PairStore.plan_rows)
 
     def loader(self, batch, seed, noise_generator=None, shuffle=None):
         return MeshLoader(self, batch, seed, noise_generator, shuffle)
@@ -308,17 +266,4 @@ class MeshStore(SampleStore):
 class MeshLoader(StoreLoader):
     """``StoreLoader`` over a ``MeshStore``: the same epochs, ``shuffle``, ``shard`` and partial last batch; the rows of batch
     ``step`` of epoch ``epoch`` are nsdp_mesh_batch_sample's for (seed, epoch, step), so two loaders with one seed give equal
-    batches.  One plan copy per epoch, one launch per batch, nothing read back."""
-
-    def _batches(self, steps):
-        st = self.store
-        epoch, self.epoch = self.epoch, self.epoch + 1
-        samples = self.epoch_samples(epoch)
-        plan = torch.from_numpy(np.ascontiguousarray(st.pair_frames[samples].T, dtype=np.int32)).to(st.device, non_blocking=True)
-        level = float(st.cfg_data["noise_level"])
-        for step in steps:
-            lo, hi = step * self.batch, min((step + 1) * self.batch, len(samples))
-            noise = None
-            if level > 0.0:
-                noise = torch.randn((hi - lo, st.n, 3), device=st.device, generator=self.noise_generator)
-            yield st.assemble(plan[:, lo:hi].contiguous(), self.seed, epoch, step, noise)
+    batches.  One plan copy per epoch, one launch per batch, nothing read back.  Nothing is overridden: the loader asks its store."""

@@ -297,36 +297,32 @@ def main(argv=None):
     return 0
 
 
-def dataset_loaders(config, seed, device, log=print):
-    """The reference's train.py:105-135 over device-resident stores: (train loader, validation loader).  Every rank builds both
-    stores whole and takes its share of the batches (StoreLoader.shard); the validation loader does not shuffle."""
-    from .datastore import SampleStore
+def _store_loaders(store_class, frames, config, seed, device, log):
+    """(train loader, validation loader) over two device-resident stores of ``store_class``; ``frames``: how the log line counts
+    a store's frames and megabytes.  Every rank builds both stores whole and takes its share of the batches (StoreLoader.shard);
+    the validation loader does not shuffle."""
     loaders = []
-    for section, default_batch, what in (("training", 16, "training"), ("validation", 1, "validation")):
+    for section, default_batch in (("training", 16), ("validation", 1)):
         sec = config[section]
-        store = SampleStore(config, sec["iden_split"], sec["motion_split"], num_sampled_pairs=sec.get("num_sampled_pairs", -1),
+        store = store_class(config, sec["iden_split"], sec["motion_split"], num_sampled_pairs=sec.get("num_sampled_pairs", -1),
                             device=device, load_mesh=sec.get("load_mesh", False))
-        log("Loaded {} {} deformation pairs ({} frames, {:.1f} MB on the device)".format(len(store), what, len(store.frames),
-                                                                                      store.nbytes / 1e6))
+        log(("Loaded {} {} deformation pairs (" + frames + " on the device)").format(len(store), section, len(store.frames),
+                                                                                   store.nbytes / 1e6))
         loaders.append(store.loader(sec.get("batch_size", default_batch), seed if section == "training" else seed + 10000,
                                     noise_generator=None, shuffle=section == "training"))
     return tuple(loaders)
+
+
+def dataset_loaders(config, seed, device, log=print):
+    """The reference's train.py:105-135 over device-resident stores of pre-sampled frames (nsdp_amd.datastore)."""
+    from .datastore import SampleStore
+    return _store_loaders(SampleStore, "{} frames, {:.1f} MB", config, seed, device, log)
 
 
 def mesh_dataset_loaders(config, seed, device, log=print):
-    """``dataset_loaders`` over device-resident MESH stores (nsdp_amd.meshstore): (train loader, validation loader) with the same
-    splits, batch sizes, seeds and shuffling; every rank builds both stores whole and takes its share of the batches."""
+    """``dataset_loaders`` over device-resident MESH stores (nsdp_amd.meshstore): the same splits, batch sizes, seeds and shuffling."""
     from .meshstore import MeshStore
-    loaders = []
-    for section, default_batch, what in (("training", 16, "training"), ("validation", 1, "validation")):
-        sec = config[section]
-        store = MeshStore(config, sec["iden_split"], sec["motion_split"], num_sampled_pairs=sec.get("num_sampled_pairs", -1),
-                          device=device, load_mesh=sec.get("load_mesh", False))
-        log("Loaded {} {} deformation pairs ({} mesh frames, {:.2f} MB on the device)".format(len(store), what, len(store.frames),
-                                                                                           store.nbytes / 1e6))
-        loaders.append(store.loader(sec.get("batch_size", default_batch), seed if section == "training" else seed + 10000,
-                                    noise_generator=None, shuffle=section == "training"))
-    return tuple(loaders)
+    return _store_loaders(MeshStore, "{} mesh frames, {:.2f} MB", config, seed, device, log)
 
 
 def synthetic_loaders(args, world):

@@ -26,7 +26,7 @@ def _frame(first, count, topo, thr_first, box):
 
 @pytest.mark.parametrize("with_noise,n,m", [(True, 300, 261), (False, 300, 0), (False, 0, 70)])
 def test_sample_inside_the_arena(with_noise, n, m):
-    from nsdp_amd import meshstore
+    from nsdp_amd import datastore, meshstore
     g = np.random.RandomState(11)
     V, FR, TR, B = 500, 400, 350, 5                 # more than one 256-lane block per part, neither a multiple of it
     verts = np.zeros((V, 4), np.float32)
@@ -55,7 +55,7 @@ def test_sample_inside_the_arena(with_noise, n, m):
     t_ids = a.input("frame_ids", torch.from_numpy(ids))
     t_noise = a.input("noise", torch.from_numpy(noise)) if with_noise else None
     key = ((7 << 32) | 5, 3, 9)
-    with a.routed(meshstore):
+    with a.routed(meshstore, datastore):      # (the outputs are datastore._batch_outputs', for both launches)
         out = meshstore.mesh_batch_sample(t["vert_arena"], t["face_arena"], t["thr_arena"], t["frame_table"], t["topo_table"], t_ids, n, m,
                                           *key, 0.1, 0.1, 0.02, t_noise, 0.02 if with_noise else 0.0)
     _SEEN.update(a.called)

@@ -159,6 +159,12 @@ def test_pair_rules_are_the_sample_stores(tmp_path):
     assert meshstore.form_pairs is datastore.form_pairs and issubclass(meshstore.MeshLoader, datastore.StoreLoader)
     assert meshstore.MeshLoader.epoch_samples is datastore.StoreLoader.epoch_samples      # (imported, not copied)
     assert meshstore.MeshLoader.shard is datastore.StoreLoader.shard
+    # one store core: both stores derive from it, neither from the other, and what they share is the same function objects
+    assert issubclass(meshstore.MeshStore, datastore.PairStore) and issubclass(datastore.SampleStore, datastore.PairStore)
+    assert datastore.SampleStore not in meshstore.MeshStore.__mro__
+    for name in ("sample_indices", "order_after", "frame_bbox"):
+        assert getattr(meshstore.MeshStore, name) is getattr(datastore.SampleStore, name) is getattr(datastore.PairStore, name), name
+    assert meshstore.MeshLoader._batches is datastore.StoreLoader._batches
 
 
 def test_vertices_are_normalised_in_float64_and_rounded_once(tmp_path):

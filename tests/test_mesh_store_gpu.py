@@ -112,6 +112,38 @@ def test_another_key_gives_other_rows(three_topologies):
         assert not torch.equal(base["space_samples_cano"], other["space_samples_cano"]), key
 
 
+def test_both_batch_kernels_write_a_row_identically():
+    """csrc/batch_rows.h is one definition: the rows that nsdp_mesh_batch_sample draws, laid out as fp32 sample pools and handed
+    to nsdp_batch_assemble with the same box, range and noise, come back as the same eleven tensors bit for bit.  B = 3, n = 300,
+    m = 70: more than one 256-lane block of surface rows, neither count a multiple of 256."""
+    from nsdp_amd import datastore
+    B, n, m, key, level = 3, 300, 70, (21, 1, 6), 0.02
+    verts, faces = mr.grid()
+    arrays = meshstore.pack([mr.deform(verts, k).astype(np.float32) for k in range(5)], [0] * 5, [faces], [0, 1, 2])
+    dev = _upload(arrays)
+    ids = np.array([[0, 1, 2], [1, 2, 3], [2, 3, 4]], dtype=np.int32)                   # (cano, src, tgt) of the three samples
+    clean = _launch(dev, ids, n, m, key)
+    # sample b's pools: frames 3b (cano), 3b + 1 (src), 3b + 2 (tgt), each of n surface records [point | normal] and m space
+    # records [point | 0]; every entry of the sample carries the box of its canonical MESH frame
+    surf = torch.cat([torch.cat([clean[f"surface_samples_{k}"][b], clean[f"surface_normals_{k}"][b]], dim=1)
+                      for b in range(B) for k in ("cano", "src", "tgt")]).contiguous()
+    space = torch.cat([torch.nn.functional.pad(clean[f"space_samples_{k}"][b], (0, 1)) for b in range(B) for k in ("cano", "src", "tgt")]).contiguous()
+    assert surf.shape == (9 * n, 6) and space.shape == (9 * m, 4) and surf.dtype == space.dtype == torch.float32
+    table = np.zeros((9, 6), dtype=np.int64)
+    for f in range(9):
+        table[f, :3] = f * n, f * m, n | (m << 32)
+        table[f, 3:6] = arrays["frame_table"][ids[0, f // 3], 3:6]
+    pool_ids = torch.arange(9, dtype=torch.int32, device=DEV).reshape(B, 3).T.contiguous()
+    surf_idx = torch.arange(n, dtype=torch.int32, device=DEV).repeat(B, 1)
+    noise = np.random.RandomState(8).randn(B, n, 3).astype(np.float32)
+    pooled = datastore.batch_assemble(surf, space, torch.from_numpy(table).to(DEV), pool_ids, surf_idx, None, m, PARTIAL_RANGE,
+                                      torch.from_numpy(noise).to(DEV), level)
+    sampled = _launch(dev, ids, n, m, key, noise, level)
+    _assert_bit_equal(pooled, {k: v.cpu().numpy() for k, v in sampled.items()})         # (fp32 as uint32, the mask as bytes)
+    assert 0 < sampled["cano_handle_sample_idx"].float().mean() < 1                     # the rule decides both ways
+    assert (sampled["surface_samples_src"] != clean["surface_samples_src"]).any()       # the noise is there
+
+
 # ------------------------------------------------------------------------------------------------------------------ correspondence
 def test_a_face_index_is_the_correspondence():
     # src == tgt frame: the same rows, bit for bit
