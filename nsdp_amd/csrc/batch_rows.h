@@ -1,7 +1,8 @@
 // The rows of a training batch (include/nsdp_batch.h, include/nsdp_meshbatch.h): the reference's per-sample tensor contract --
 // source noise, the handle mask against the canonical box, the six surface planes, the 7-wide input row, the three space planes
 // -- and the argument checks that go with it, one definition for batch_assemble.hip (rows fetched from sample pools) and
-// mesh_sample.hip (rows sampled from triangles), beside draw_key.h.  Include it ONLY from translation units built with
+// mesh_sample.hip (rows sampled from triangles), beside draw_key.h; mesh_whole.hip (include/nsdp_meshwhole.h: every VERTEX of a
+// batch's meshes) takes the handle rule and the input row from here as well.  Include it ONLY from translation units built with
 // -ffp-contract=off: the arithmetic is one rounding per operation (spelled with the __f*_rn intrinsics), and a row carries the
 // same bits from both kernels because both run this text under that flag.
 //
@@ -50,6 +51,18 @@ __device__ __forceinline__ bool is_handle(const float *cano, const CanoBox &box,
   return head | tail | foot;
 }
 
+// The 7-wide input row [src | tgt * mask | mask] at `in`: ONE multiply per target component (-x * 0 = -0), whoever writes the row
+// (write_surface_row below for sampled rows, mesh_whole.hip for whole meshes).
+__device__ __forceinline__ void write_inputs_row(float *in, const float *sp, const float *tp, bool handle) {
+  const float mf = handle ? 1.f : 0.f;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    in[k] = sp[k];
+    in[3 + k] = __fmul_rn(tp[k], mf);
+  }
+  in[6] = mf;
+}
+
 // Surface row `row` (= b * n + j) of a batch of B x n: the six planes of [6, B, n, 3] (points, then normals, of the canonical,
 // source and target frame), the mask byte of [B, n, 1] and the input row [src | tgt * mask | mask] of [B, n, 7], the source
 // point with `noise_level * noise[row]` added -- in `sp` itself, which the caller gives up: a copy of it costs the pool kernel two
@@ -63,7 +76,6 @@ __device__ __forceinline__ void write_surface_row(const RowArgs &a, int B, int n
     for (int k = 0; k < 3; ++k) sp[k] = __fadd_rn(sp[k], __fmul_rn(a.noise_level, z[k]));
   }
   const bool handle = is_handle(cp, box, a.partial_range);
-  const float mf = handle ? 1.f : 0.f;
   const size_t plane = static_cast<size_t>(B) * n * 3;
   float *o = a.surface_out + row * 3;
 #pragma unroll
@@ -76,13 +88,7 @@ __device__ __forceinline__ void write_surface_row(const RowArgs &a, int B, int n
     o[5 * plane + k] = tn[k];
   }
   a.handle_out[row] = handle ? 1 : 0;
-  float *in = a.inputs_out + row * 7;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    in[k] = sp[k];
-    in[3 + k] = __fmul_rn(tp[k], mf);
-  }
-  in[6] = mf;
+  write_inputs_row(a.inputs_out + row * 7, sp, tp, handle);
 }
 
 // Space row `row` (= b * m + j) of a batch of B x m: the three planes of [3, B, m, 3].

@@ -14,8 +14,10 @@ Every rank of a data-parallel job holds the WHOLE store (each rank's loader take
 larger than its byte budget is refused, by name, before anything is allocated on the device.  What does not depend on a frame
 being a sample pool is ``PairStore``, the core that ``meshstore.MeshStore`` derives from as well.
 
-Out of scope, refused by name: the user-handle data sets (``tosca``, ``dogrec``) and ``load_mesh`` (they need meshes),
-``partial_shape_ratio < 1`` (the reference's own call site cannot run, see dataset.py), stores larger than device memory.
+Out of scope for THIS store, refused by name: the user-handle data sets (``tosca``, ``dogrec``) and ``load_mesh`` -- they need
+meshes, which ``meshstore`` holds (``HandleMeshStore``; ``MeshStore.whole_meshes``, and nsdp_amd/evaluate.py walks a test split
+with them) -- ``partial_shape_ratio < 1`` (the reference's own call site cannot run, see dataset.py), stores larger than device
+memory.
 """
 from __future__ import annotations
 
@@ -35,6 +37,7 @@ SURFACE, SPACE = 0, 1                  # nsdp_subset_draw's `which`
 MAX_ROWS = 1 << 20                     # NSDP_BATCH_MAX_ROWS
 SURFACE_RECORD, SPACE_RECORD = 6, 4    # elements per arena record
 _KEYS = ("cano", "src", "tgt")
+FLOW_KINDS, HANDLE_KINDS = ("deform4d", "deformtransfer"), ("tosca", "dogrec")      # data.type: sequences of frames / single meshes to drag
 
 
 class DataStoreError(ValueError):
@@ -64,6 +67,8 @@ def form_pairs(cfg_data: dict, iden_split: str, motion_split: str, refuse=None) 
     (idx_cano, cano sequence, cano frame, idx_motion, source sequence, source frame, target sequence, target frame).
     ``deform4d``: dataset_deform4d_flow.py:37-117; ``deformtransfer``: dataset_deformtransfer_flow.py:38-116 (no identity list:
     a sequence is its own canonical sequence; ``arbitrary`` has the evaluation rule only, with the per-animal source frame).
+    ``tosca`` / ``dogrec`` (the user-handle data sets, dataset_userhandle_flow.py:39-95; ``meshstore.HandleMeshStore`` alone asks
+    for them): every listed directory gives ONE pair whose canonical, source and target frame are all its frame 0000.
     ``refuse``: the store's refusal, for a missing split list (default: ``SampleStore``'s)."""
     refuse = refuse or SampleStore._refuse
     kind = cfg_data["type"]
@@ -88,6 +93,9 @@ def form_pairs(cfg_data: dict, iden_split: str, motion_split: str, refuse=None) 
         else:
             idx_cano, cano_seq = motion_index[seq], seq
         idx_motion = motion_index[seq]
+        if kind in HANDLE_KINDS:      # (dataset_userhandle_flow.py:72-95: the mesh itself, dragged; no frame list is read)
+            pairs.append((idx_cano, cano_seq, "0000", idx_motion, seq, "0000", seq, "0000"))
+            continue
         frames = _frame_names(cfg_data, seq)
         if cfg_data["arbitrary"]:
             if kind == "deform4d" and train:
@@ -234,6 +242,7 @@ class PairStore:
     _error = DataStoreError
     # why THIS store cannot serve what every store refuses by name: the user-handle data sets, load_mesh, partial shapes
     _refused = (None, None, None)
+    _kinds = FLOW_KINDS      # the data.type values this store reads (meshstore.HandleMeshStore: HANDLE_KINDS)
 
     def __init__(self, config, iden_split, motion_split, num_sampled_pairs, load_mesh):
         data = config["data"]
@@ -242,10 +251,10 @@ class PairStore:
         self.is_train = motion_split[:5] == "train"
         kind = data.get("type")
         no_handles, no_load_mesh, no_partial = self._refused
-        if kind in ("tosca", "dogrec"):
+        if kind in HANDLE_KINDS and kind not in self._kinds:
             self._refuse(f"data type '{kind}' (the user-handle data sets) {no_handles}")
-        if kind not in ("deform4d", "deformtransfer"):
-            self._refuse(f"unknown data type '{kind}' (deform4d and deformtransfer are read)")
+        if kind not in self._kinds:
+            self._refuse(f"unknown data type '{kind}' ({' and '.join(self._kinds)} are read)")
         if load_mesh:
             self._refuse(no_load_mesh)
         if data.get("partial_shape_ratio", 1.0) < 1.0:

@@ -1,0 +1,252 @@
+"""Test-split evaluation from the device-resident mesh store: the reference's test.py loop (and, for the user-handle data sets,
+its run.py loop) over packed batches of whole meshes of different sizes.
+
+    python -m nsdp_amd.evaluate CONFIG [--batch N] [--weight_file F] [--seed S] [--limit K]
+
+The reference walks its test split one pair at a time: it loads three meshes on the host, deforms every vertex of the source,
+computes the metrics with one ``.item()`` each and writes five mesh files.  Here the split's frames are resident on the device
+(nsdp_amd.meshstore); a batch of ``--batch`` pairs of DIFFERENT vertex counts is one launch of nsdp_mesh_batch_whole beside the
+sampled clouds (``MeshStore.eval_loader``), one packed decode (nsdp_amd.ragged), one ``compute_evaluation_metrics_batch`` and
+ONE ``.tolist()``; mesh export takes one device-to-host copy per batch.
+
+The store is built from ``config["test"]``: ``iden_split``, ``motion_split``, ``num_sampled_pairs``; ``batch_size`` is the
+default of ``--batch`` and ``weight_file`` that of ``--weight_file``.  Without a weight file the best checkpoint of the
+experiment directory (``config["experiment"]``: ``out_dir`` / ``name``) is loaded, ``checkpoints.load_best_checkpoints``.
+
+Output, in the experiment directory:
+  <motion_split>.txt    one line per pair and a closing line of means.  Like the reference's loop (test.py:136-139) a metric
+                        enters its mean only where its value is <= 1.0; how many values were left out is printed;
+  <motion_split>.json   every per-pair value unfiltered, with the pair's names;
+  <motion_split>/<mesh_folder>/{source,canonical,deformed,target,handle}/   with ``test.generate_mesh``: the meshes through
+                        ``meshio.write_mesh`` under the reference's file names (utils/generation.py:11-35), vertices grey 0.75,
+                        handle vertices red on source and canonical and blue on target; the handle mesh is the target's faces
+                        whose three vertices are all handles; the deformed mesh is written uncoloured (no error colour map).
+A pair's ``loss`` is what the step function returns for the BATCH the pair was in (the mean over its shapes of
+compute_l2_error); at ``--batch 1`` it is the pair's own, as in the reference.
+
+``data.type`` ``tosca`` / ``dogrec`` (``meshstore.HandleMeshStore``) is the reference's run.py: every batch opens a
+``RaggedEditSession`` on its packed vertices -- the cloud being each mesh's own vertex set -- drags with
+``HandleSpec.from_config(config["data"])``, exports the source, deformed, target and handle meshes into a folder named after the
+drag (``drag_folder_name``), and computes no metrics.
+
+Refused by name: ``test.generate_pointcloud`` (point-cloud export).  Out of scope: ``--gpus N``, graph replay of the whole step.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+METRICS = ("l2", "fnc", "cd")
+PARTS = ("source", "canonical", "deformed", "target", "handle")
+GREY, RED, BLUE = (191, 191, 191), (255, 0, 0), (0, 0, 255)      # ((0.75 * 255).astype(uint8) = 191, as the reference rounds it)
+
+
+class EvaluateError(ValueError):
+    pass
+
+
+# ---------------------------------------------------------------------------------------------------------------- names
+def export_names(pair_info, ext) -> dict:
+    """The five files of a pair, relative to the mesh folder (utils/generation.py:11-35): ``<seq>_<frame>.<ext>`` for source and
+    canonical, ``<src_seq>_<src_frame>_to_<tgt_seq>_<tgt_frame>.<ext>`` for deformed, target and handle."""
+    _, cano_seq, cano_frame, _, src_seq, src_frame, tgt_seq, tgt_frame = pair_info
+    pair = f"{src_seq}_{src_frame}_to_{tgt_seq}_{tgt_frame}.{ext}"
+    return {"source": os.path.join("source", f"{src_seq}_{src_frame}.{ext}"),
+            "canonical": os.path.join("canonical", f"{cano_seq}_{cano_frame}.{ext}"),
+            "deformed": os.path.join("deformed", pair), "target": os.path.join("target", pair), "handle": os.path.join("handle", pair)}
+
+
+def drag_folder_name(data_cfg) -> str:
+    """utils/generation.py:129-161: ``drag``, the first part that is set, ``_x%.2fy%.2fz%.2f``, ``_ratio%.2f``, ``_cliptail``."""
+    from .edit import PARTS as HANDLE_PARTS
+    uh = data_cfg["userhandle"]
+    name = "drag" + next(("_" + p for p in HANDLE_PARTS if uh.get(p)), "")
+    name += "_x%.2fy%.2fz%.2f" % (uh["xtrans"], uh["ytrans"], uh["ztrans"])
+    name += "_ratio%.2f" % data_cfg["partial_range"]
+    return name + ("_cliptail" if uh.get("cliptail") else "")
+
+
+def filtered_means(rows, keys=METRICS):
+    """(means, left_out) over per-pair dicts: a value enters its key's mean only where it is <= 1.0 (test.py:138; a NaN does not);
+    ``left_out[key]`` counts the others.  A key without a value that entered has the mean NaN."""
+    means, left_out = {}, {}
+    for k in keys:
+        kept = [r[k] for r in rows if r[k] <= 1.0]
+        means[k] = float(np.mean(kept)) if kept else float("nan")
+        left_out[k] = len(rows) - len(kept)
+    return means, left_out
+
+
+def refuse_pointclouds(config):
+    if config.get("test", {}).get("generate_pointcloud"):
+        raise EvaluateError("evaluate: test.generate_pointcloud (point-cloud export) is not supported; set it to false "
+                            "(test.generate_mesh writes the meshes)")
+
+
+def metric_samples(pred, faces, count, seed, step):
+    """The surface draws of batch ``step``: ``sample_surface_batch`` on the predicted meshes with a generator seeded by
+    (seed, step), so that a batch's metrics can be reproduced from its predictions."""
+    from .eval_metric import sample_surface_batch
+    g = torch.Generator(device=pred.device).manual_seed((int(seed) * 1000003 + int(step)) & 0x7FFFFFFFFFFFFFFF)
+    return sample_surface_batch(pred.like(pred.packed.detach()), faces, int(count), g)
+
+
+# ---------------------------------------------------------------------------------------------------------------- export
+def _to_host(vertex_sets, handle, faces):
+    """ONE device-to-host copy of what a batch's export needs: the [cap, 3] fp32 vertex sets, the [cap] handle flags and the
+    [fcap, 3] int32 faces travel as the words of one int32 tensor."""
+    parts = [v.contiguous().view(torch.int32).reshape(-1) for v in vertex_sets]
+    parts += [handle.reshape(-1).to(torch.int32), faces.contiguous().reshape(-1)]
+    flat = torch.cat(parts).cpu().numpy()
+    cap, at, out = vertex_sets[0].shape[0], 0, []
+    for _ in vertex_sets:
+        out.append(flat[at:at + cap * 3].view(np.float32).reshape(cap, 3))
+        at += cap * 3
+    return out, flat[at:at + cap].astype(bool), flat[at + cap:].reshape(-1, 3)
+
+
+def export_meshes(directory, pair_infos, ext, verts, handle, faces, vert_counts, face_counts):
+    """Write the meshes of a batch that is already on the host.  ``verts``: part -> [cap, 3] fp32 for "source", "deformed",
+    "target" and, where it is exported, "canonical"; ``handle`` [cap] bool; ``faces`` [fcap, 3] int32, local indices."""
+    from .meshio import write_mesh
+    v0 = f0 = 0
+    for info, nv, nf in zip(pair_infos, vert_counts, face_counts):
+        names = export_names(info, ext)
+        h, f = handle[v0:v0 + nv], faces[f0:f0 + nf]
+        red, blue = np.tile(np.array(GREY, np.uint8), (nv, 1)), np.tile(np.array(GREY, np.uint8), (nv, 1))
+        red[h], blue[h] = RED, BLUE
+        for part, of, colors, sel in (("source", "source", red, f), ("canonical", "canonical", red, f), ("deformed", "deformed", None, f),
+                                      ("target", "target", blue, f), ("handle", "target", blue, f[h[f].all(axis=1)])):
+            if verts.get(of) is None:
+                continue
+            path = os.path.join(directory, names[part])
+            os.makedirs(os.path.dirname(path), exist_ok=True)
+            write_mesh(path, verts[of][v0:v0 + nv], sel, colors)
+        v0, f0 = v0 + nv, f0 + nf
+
+
+# ---------------------------------------------------------------------------------------------------------------- the loops
+def evaluate(model, test_fn, store, config, experiment_directory, batch, seed, log=print, limit=None) -> list:
+    """The loop of the module docstring over ``store`` (a ``meshstore.MeshStore`` of the test split, or a ``HandleMeshStore``):
+    -> the per-pair dicts, in the split's order.  ``test_fn``: the step function of ``build_model`` (either one: both read the
+    same keys).  ``limit``: only the first ``limit`` pairs."""
+    from .meshstore import HandleMeshStore
+    refuse_pointclouds(config)
+    test = config.get("test", {})
+    os.makedirs(experiment_directory, exist_ok=True)
+    model.eval()
+    loader = store.eval_loader(batch, seed)
+    if limit is not None:
+        loader.samples = loader.samples[:max(int(limit), 0)]
+    if isinstance(store, HandleMeshStore):
+        return _drag_loop(model, store, loader, config, experiment_directory, log)
+    from .eval_metric import compute_evaluation_metrics_batch
+    split = test.get("motion_split", store.motion_split)
+    mesh_dir = os.path.join(experiment_directory, split, test.get("mesh_folder", "meshes")) if test.get("generate_mesh") else None
+    ext = test.get("mesh_format", "ply")
+    rows = []
+    with open(os.path.join(experiment_directory, split + ".txt"), "w") as txt:
+        def say(line):
+            txt.write(line + "\n")
+            log(line)
+        for step, data_dict in enumerate(loader):
+            loss, out = test_fn(model, data_dict, config, compute_loss=True)
+            pred, faces = out["verts_tgt_pred"], out["faces"]
+            samples = metric_samples(pred, faces, test.get("pointcloud_size", 30000), seed, step)
+            m = compute_evaluation_metrics_batch(out, samples=samples)
+            values = torch.stack([m[k] for k in METRICS]).tolist()      # the batch's ONE read-back of metrics
+            infos = [store.pairs[i] for i in out["index"]]
+            for b, info in enumerate(infos):
+                row = {"index": int(out["index"][b]), "pair_info": list(info), "loss": float(loss)}
+                row.update({k: values[c][b] for c, k in enumerate(METRICS)})
+                rows.append(row)
+                say("pair {:5d} {}_{} -> {}_{}  loss {:.6e}  ".format(row["index"], info[4], info[5], info[6], info[7], row["loss"])
+                    + "  ".join("{} {:.6e}".format(k, row[k]) for k in METRICS))
+            if mesh_dir is not None:
+                sets, handle, f = _to_host([out["verts_src"].packed, out["verts_cano"].packed, pred.packed.detach(),
+                                            out["verts_tgt"].packed], out["cano_handle_vert_idx"], faces.packed)
+                export_meshes(mesh_dir, infos, ext, dict(zip(("source", "canonical", "deformed", "target"), sets)), handle, f,
+                              pred.counts, faces.counts)
+        means, left_out = filtered_means(rows)
+        say("mean over {} pairs (values <= 1.0 only)  ".format(len(rows)) + "  ".join("{} {:.6e}".format(k, means[k]) for k in METRICS)
+            + "  left out: " + ", ".join("{} {}".format(k, left_out[k]) for k in METRICS))
+    with open(os.path.join(experiment_directory, split + ".json"), "w") as f:
+        json.dump({"pairs": rows, "means": means, "left_out": left_out}, f, indent=1)
+    return rows
+
+
+@torch.no_grad()
+def _drag_loop(model, store, loader, config, experiment_directory, log):
+    """run.py:119-139 over packed batches: one RaggedEditSession per batch, one drag, four meshes per pair, no metrics."""
+    from .edit import HandleSpec, RaggedEditSession
+    test = config.get("test", {})
+    spec = HandleSpec.from_config(config["data"])
+    mesh_dir = os.path.join(experiment_directory, drag_folder_name(config["data"]), test.get("mesh_folder", "meshes"))
+    ext = test.get("mesh_format", "ply")
+    rows = []
+    for data_dict in loader:
+        src, faces = data_dict["verts_src"], data_dict["faces"]
+        with RaggedEditSession(model, src, partial_range=spec.partial_range, cliptail=spec.cliptail) as session:
+            out = session.drag(spec)
+            infos = [store.pairs[i] for i in data_dict["index"]]
+            if test.get("generate_mesh", True):
+                sets, handle, f = _to_host([src.packed, out["verts_tgt_pred"].packed, out["verts_tgt"].packed],
+                                           out["cano_handle_vert_idx"].packed, faces.packed)
+                export_meshes(mesh_dir, infos, ext, dict(zip(("source", "deformed", "target"), sets)), handle, f, src.counts, faces.counts)
+        for i, info in zip(data_dict["index"], infos):
+            rows.append({"index": int(i), "pair_info": list(info)})
+            log("dragged {} ({}) -> {}".format(info[4], spec.part, os.path.join(mesh_dir, export_names(info, ext)["deformed"])))
+    return rows
+
+
+def build_parser():
+    ap = argparse.ArgumentParser(description="Evaluate a deformation network on the test split of a mesh data set (MI355X)")
+    ap.add_argument("config_file")
+    ap.add_argument("--batch", type=int, default=None, help="pairs per packed batch (default: test.batch_size of the config, else 1)")
+    ap.add_argument("--weight_file", default=None, help="overrides test.weight_file; without either the experiment's best checkpoint")
+    ap.add_argument("--seed", type=int, default=27, help="of the sampled clouds and of the metrics' surface draws")
+    ap.add_argument("--limit", type=int, default=None, metavar="K", help="only the first K pairs of the split")
+    return ap
+
+
+def main(argv=None):
+    import yaml
+    from .checkpoints import load_best_checkpoints
+    from .meshstore import HandleMeshStore, MeshStore
+    from .datastore import HANDLE_KINDS
+    from .model import build_model
+    args = build_parser().parse_args(sys.argv[1:] if argv is None else argv)
+    with open(args.config_file) as f:
+        config = yaml.safe_load(f)
+    try:
+        refuse_pointclouds(config)
+    except EvaluateError as e:
+        sys.exit(f"nsdp_amd.evaluate: {e}")
+    test = config["test"]
+    experiment_directory = os.path.join(config["experiment"]["out_dir"], config["experiment"]["name"])
+    os.makedirs(experiment_directory, exist_ok=True)
+    device = torch.device("cuda", 0)
+    weight_file = args.weight_file or test.get("weight_file")
+    model, _, _, test_fn = build_model(config, weight_file, device=device)
+    if weight_file is None:
+        args.continue_from_epoch = None
+        load_best_checkpoints(model, experiment_directory, args, device)
+        if args.continue_from_epoch is None:
+            print(f"WARNING: no weight file and no modelbest_* checkpoint in {experiment_directory}: the weights are random")
+    store_class = HandleMeshStore if config["data"].get("type") in HANDLE_KINDS else MeshStore
+    store = store_class(config, test.get("iden_split"), test["motion_split"], num_sampled_pairs=test.get("num_sampled_pairs", -1),
+                        device=device)
+    print("Loaded {} test deformation pairs ({} mesh frames, {:.2f} MB on the device)".format(len(store), len(store.frames),
+                                                                                            store.nbytes / 1e6))
+    rows = evaluate(model, test_fn, store, config, experiment_directory, args.batch or test.get("batch_size", 1), args.seed,
+                    limit=args.limit)
+    return 0 if rows else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -263,3 +263,33 @@ def write_mesh_dataset_tree(root, meshes: dict, motions, frames, mesh_file="mesh
             "inverse": False, "fix_coord_system": False, "num_surf_samples": 256, "num_space_samples": 128,
             "partial_range": 0.1, "noise_level": 0.0, "partial_shape_ratio": 1.0, "norm_params_file": norm_params_file,
             "mesh_file": mesh_file, "space_sigma": [0.1, 0.02]}
+
+
+def write_handle_mesh_tree(root, meshes: dict, data_type="tosca", mesh_file="mesh_norm.ply", split="test", userhandle=None,
+                           norm_params_file="orig_to_gaps.txt"):
+    """A procedural user-handle data set (dataset/dataset_userhandle_flow.py: ``tosca`` / ``dogrec``) -- single meshes to drag:
+
+        root/dataset/<name>/0000/{mesh_file, norm_params_file}        root/splits/<data_type>/<split>.lst
+
+    ``meshes``: name -> (verts (V, 3), faces (F, 3)); the files hold fp32 vertices and the identity as norm_params_file.
+    ``userhandle``: the drag's settings (default: the head by (-0.15, -0.2, -0.2), the reference's config/tosca/head.yaml).
+    Returns the ``data`` section of a config that reads the tree through ``meshstore.HandleMeshStore``."""
+    import os
+    from .meshio import write_mesh
+    if data_type not in ("tosca", "dogrec"):
+        raise ValueError(f"write_handle_mesh_tree: data_type '{data_type}' is neither 'tosca' nor 'dogrec'")
+    dataset_dir, split_dir = os.path.join(root, "dataset"), os.path.join(root, "splits")
+    for name, (verts, faces) in meshes.items():
+        d = os.path.join(dataset_dir, str(name), "0000")
+        os.makedirs(d, exist_ok=True)
+        write_mesh(os.path.join(d, mesh_file), np.asarray(verts).astype(np.float32), faces)
+        np.savetxt(os.path.join(d, norm_params_file), np.eye(4))
+    os.makedirs(os.path.join(split_dir, data_type), exist_ok=True)
+    with open(os.path.join(split_dir, data_type, split + ".lst"), "w") as f:
+        f.write("\n".join(str(n) for n in meshes) + "\n")
+    handle = {"head": True, "tail": False, "frontleftfoot": False, "frontrightfoot": False, "behindleftfoot": False,
+              "behindrightfoot": False, "cliptail": False, "xtrans": -0.15, "ytrans": -0.2, "ztrans": -0.2}
+    handle.update(userhandle or {})
+    return {"type": data_type, "dataset_dir": dataset_dir, "split_dir": split_dir, "interval": 1, "arbitrary": True, "inverse": False,
+            "fix_coord_system": False, "num_surf_samples": 0, "num_space_samples": 0, "partial_range": 0.1, "noise_level": 0.0,
+            "partial_shape_ratio": 1.0, "norm_params_file": norm_params_file, "mesh_file": mesh_file, "userhandle": handle}

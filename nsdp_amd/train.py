@@ -6,9 +6,10 @@ data set on disk that ``config["data"]`` names (nsdp_amd.datastore: the referenc
 frame resident on the device, the splits and batch sizes of the config's ``training`` / ``validation`` sections as in the
 reference's train.py:105-135); ``--mesh-dataset`` trains from the MESH sequences of the same layout (nsdp_amd.meshstore:
 ``data["mesh_file"]`` of every frame resident on the device, surface and space rows sampled afresh inside every batch's launch:
-no pre-sampled point files); ``--synthetic`` (the default) uses procedural batches.  Not read from disk: the user-handle data
-sets (``tosca``, ``dogrec``), ``load_mesh`` batches (whole meshes beside the samples), partial shapes, and a data set larger
-than the device's memory.
+no pre-sampled point files); ``--synthetic`` (the default) uses procedural batches.  Training reads no whole meshes
+(``load_mesh``) and not the user-handle data sets (``tosca``, ``dogrec``): those belong to evaluation, ``python -m
+nsdp_amd.evaluate CONFIG`` (the test split from the mesh store in packed whole-mesh batches; the reference's test.py and run.py).
+Not read from disk at all: partial shapes, and a data set larger than the device's memory.
 
     python -m nsdp_amd.train config.yaml experiment_dir [--synthetic 4] [--epochs 2]
     python -m nsdp_amd.train config.yaml experiment_dir --dataset [--graph] [--gpus N]
