@@ -45,8 +45,8 @@ const char *nsdp_last_error(void);
  * launches that run on a side stream next to the critical chain and resets it to 0 (the workspace query sees the same value).
  * The hint is THREAD-LOCAL: it applies to launches made by the host thread that set it (set / query / launch / reset happen on
  * one thread; another device's backward thread cannot clobber it).
- * 10: 0 = immediate-insertion kNN kernel; 11: 0 = three-launch BatchNorm forms (A/B against the one-launch slab kernels), 2 = slab kernels up to 16384 rows;
- * 12: 0 = one-lane-per-query ball_query / three_nn kernels (A/B against the four-lane plane-tile scans). */
+ * 11: 0 = three-launch BatchNorm forms (A/B against the one-launch slab kernels), 2 = slab kernels up to 16384 rows;
+ * 10, 12: retired, ignored. */
 void nsdp_debug_set(int key, int value);
 /* Number of HIP devices visible (0 when there is none; never fails). */
 int nsdp_device_count(void);

@@ -3,11 +3,10 @@
 //
 // nn_dist2: knn.hip at k = 1 without what the top-k kernels carry -- no sorted list, no insertion branch and, for the metric,
 // no index.  MI355X design:
-//   * the source streams through LDS as three coordinate planes with sentinel padding (x = FLT_MAX squares to +inf, which no
-//     minimum admits): four candidates are three 16-byte broadcast reads, no range checks in the scan;
-//   * a lane holds kQ = 4 queries in registers, so one LDS read serves four distance tests; two candidates per packed fp32
-//     instruction, ((dx*dx + dy*dy) + dz*dz), dx = query - source, one rounding per operation (contraction is off): the
-//     bits of nsdp::sq_dist3, hence of nsdp_knn;
+//   * the source streams through LDS as the plane tile of plane_tile.h (three coordinate planes, sentinels no minimum admits):
+//     four candidates are three 16-byte broadcast reads, no range checks in the scan;
+//   * a lane holds kQ = 4 queries in registers, so one LDS read serves four distance tests; the distances are plane_tile.h's
+//     dist4: the bits of nsdp::sq_dist3, hence of nsdp_knn;
 //   * without an index the source range is split over workgroups (grid y) until the grid fills the chip, and the partial
 //     minima meet in dist2_out by an INTEGER minimum on the distance bits -- d2 >= 0 makes unsigned order float order, so the
 //     result is exact and independent of the order of arrival.  dist2_out is initialised by a kernel of the same call.
@@ -23,6 +22,7 @@
 #include "../../include/nsdp_eval.h"
 #include "common.h"
 #include "list_reduce.h"
+#include "plane_tile.h"
 #include "prof.h"
 #include "ragged.h"
 
@@ -36,8 +36,6 @@ constexpr int kQ = 4;                      // queries per lane
 constexpr int kQueryTile = kThreads * kQ;  // queries per workgroup (1024)
 constexpr int kTile = 1024;                // source rows per LDS tile (12 KiB in three planes)
 constexpr int kPad = 4;                    // sentinel entries behind the last row: the scan takes four rows at a time
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // One workgroup's search.  Queries: rows [row0, min(row0 + kQueryTile, end)) of `query` (row r at query + 3 r); lane t holds rows
 // row0 + t + 256 q.  Source: rows [c0, c1) of the m rows at `source`, 0 <= c0, c1 <= m.  `combine`: the workgroup is one of
@@ -54,9 +52,7 @@ template <int kMode>
 __device__ __forceinline__ void nn_scan(const float *__restrict__ query, int row0, int end, const float *__restrict__ source,
                                         int c0, int c1, bool combine, float *__restrict__ dist2_out,
                                         int32_t *__restrict__ idx_out, int idx_base, int idx_max) {
-  __shared__ __attribute__((aligned(16))) float tx[kTile + kPad];
-  __shared__ __attribute__((aligned(16))) float ty[kTile + kPad];
-  __shared__ __attribute__((aligned(16))) float tz[kTile + kPad];
+  __shared__ nsdp::PlaneTile<kTile, kPad> tile;
   float qx[kQ], qy[kQ], qz[kQ], best[kQ];
   int bi[kQ];
 #pragma unroll
@@ -76,32 +72,15 @@ __device__ __forceinline__ void nn_scan(const float *__restrict__ query, int row
   for (int base = c0; base < c1; base += kTile) {
     const int cnt = min(kTile, c1 - base);
     __syncthreads();
-    for (int t = threadIdx.x; t < cnt; t += kThreads) {
-      const float *p = source + static_cast<size_t>(base + t) * 3;
-      tx[t] = p[0]; ty[t] = p[1]; tz[t] = p[2];
-    }
-    if (threadIdx.x < kPad) {
-      tx[cnt + threadIdx.x] = FLT_MAX; ty[cnt + threadIdx.x] = 0.f; tz[cnt + threadIdx.x] = 0.f;
-    }
+    tile.load<kThreads>(source + static_cast<size_t>(base) * 3, cnt);
     __syncthreads();
     for (int t = 0; t < cnt; t += 4) {
-      const f32x4 X = *reinterpret_cast<const f32x4 *>(&tx[t]);
-      const f32x4 Y = *reinterpret_cast<const f32x4 *>(&ty[t]);
-      const f32x4 Z = *reinterpret_cast<const f32x4 *>(&tz[t]);
-      const f32x2 x01 = {X[0], X[1]}, x23 = {X[2], X[3]}, y01 = {Y[0], Y[1]}, y23 = {Y[2], Y[3]};
-      const f32x2 z01 = {Z[0], Z[1]}, z23 = {Z[2], Z[3]};
+      nsdp::f32x4 X, Y, Z;
+      tile.read4(t, X, Y, Z);      // once for the lane's kQ queries
 #pragma unroll
       for (int q = 0; q < kQ; ++q) {
-        const f32x2 q2x = {qx[q], qx[q]}, q2y = {qy[q], qy[q]}, q2z = {qz[q], qz[q]};
-        f32x2 d01, d23;
-        {
-          const f32x2 dx = q2x - x01, dy = q2y - y01, dz = q2z - z01;
-          d01 = (dx * dx + dy * dy) + dz * dz;
-        }
-        {
-          const f32x2 dx = q2x - x23, dy = q2y - y23, dz = q2z - z23;
-          d23 = (dx * dx + dy * dy) + dz * dz;
-        }
+        nsdp::f32x2 d01, d23;
+        nsdp::dist4(X, Y, Z, qx[q], qy[q], qz[q], d01, d23);
         if constexpr (kMode == kDistIdx) {
           const float d[4] = {d01[0], d01[1], d23[0], d23[1]};
 #pragma unroll

@@ -13,8 +13,10 @@
 // (distance, index) (torch.argsort is unstable on CPU, so exact ties have no reference order).
 #include <cfloat>
 #include <climits>
+#include <type_traits>
 
 #include "common.h"
+#include "plane_tile.h"
 #include "prof.h"
 #include "ragged.h"
 
@@ -23,8 +25,6 @@
 namespace {
 
 constexpr int kTile = 1024;  // source points per LDS tile (16 KiB)
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // One lane's search: `tile` is the workgroup's LDS tile, `qp` the lane's query point (read when `active`), `source` the m
 // points of the lane's shape; the k best go to io[0..k) / dout[0..k) (dout may be NULL).  Every lane of the workgroup must
@@ -119,113 +119,22 @@ __global__ __launch_bounds__(256) void knn_ragged_kernel(const float *__restrict
               dist_all ? dist_all + row * k : nullptr);
 }
 
-// Several lanes per query.  With one lane per query the kernel is one wave per SIMD at the encoder's sizes (2048
-// queries x 32 shapes = 1024 waves) and the wave-level insertion branch fires in most iterations (any of 64 lanes
-// improving runs the unrolled shift for all): 313 us per launch whatever the batch.  Here S lanes share a query, lane s
-// scans every S-th part of each LDS tile with its own sorted top-K, and the S lists are merged through LDS by
-// (distance, index) -- the same total order, S times the waves, 1/S of the iterations per wave.
-template <int K, int S>
-__global__ __launch_bounds__(256) void knn_split_kernel(const float *__restrict__ query_all,
-                                                        const float *__restrict__ source_all, int n, int m, int k,
-                                                        int32_t *__restrict__ idx_all, float *__restrict__ dist_all) {
-  __shared__ float4 tile[kTile];
-  __shared__ float md[256 * K];
-  __shared__ int mi[256 * K];
-  constexpr int kQ = 256 / S;                    // queries per workgroup
-  const int b = blockIdx.y;
-  const float *query = query_all + static_cast<size_t>(b) * n * 3;
-  const float *source = source_all + static_cast<size_t>(b) * m * 3;
-  const int ql = threadIdx.x / S, sub = threadIdx.x - ql * S;   // S consecutive lanes share a query
-  const int i = blockIdx.x * kQ + ql;
-  const bool active = i < n;
-  float qx = 0.f, qy = 0.f, qz = 0.f;
-  if (active) {
-    qx = query[i * 3 + 0]; qy = query[i * 3 + 1]; qz = query[i * 3 + 2];
-  }
-  float bd[K];
-  int bi[K];
-#pragma unroll
-  for (int t = 0; t < K; ++t) {
-    bd[t] = FLT_MAX;
-    bi[t] = 0x7fffffff;
-  }
-  for (int base = 0; base < m; base += kTile) {
-    const int cnt = min(kTile, m - base);
-    __syncthreads();
-    for (int t = threadIdx.x; t < cnt; t += 256) {
-      const float *p = source + static_cast<size_t>(base + t) * 3;
-      tile[t] = make_float4(p[0], p[1], p[2], 0.f);
-    }
-    __syncthreads();
-    const int per = (cnt + S - 1) / S;           // lane `sub` scans tile entries [sub * per, (sub + 1) * per)
-    const int t0 = sub * per, t1 = min(cnt, t0 + per);
-    for (int t = t0; t < t1; ++t) {
-      const float4 sp = tile[t];
-      const float d = nsdp::sq_dist3(qx, qy, qz, sp.x, sp.y, sp.z);
-      if (d < bd[K - 1]) {
-        const int j = base + t;
-#pragma unroll
-        for (int u = K - 1; u > 0; --u) {
-          const bool shift = d < bd[u - 1];
-          const bool here = !shift && d < bd[u];
-          const float nd = shift ? bd[u - 1] : (here ? d : bd[u]);
-          const int ni = shift ? bi[u - 1] : (here ? j : bi[u]);
-          bd[u] = nd;
-          bi[u] = ni;
-        }
-        if (d < bd[0]) {
-          bd[0] = d;
-          bi[0] = j;
-        }
-      }
-    }
-  }
-  // A lane's list is ascending in (distance, index): strict `<` keeps the earlier (lower) index first on ties, and a
-  // lane meets its candidates in increasing index order.  S-way merge by (distance, index) on lane 0 of the query.
-#pragma unroll
-  for (int t = 0; t < K; ++t) {
-    md[threadIdx.x * K + t] = bd[t];
-    mi[threadIdx.x * K + t] = bi[t];
-  }
-  __syncthreads();
-  if (active && sub == 0) {
-    int head[S];
-#pragma unroll
-    for (int u = 0; u < S; ++u) head[u] = 0;
-    int32_t *io = idx_all + (static_cast<size_t>(b) * n + i) * k;
-    float *dout = dist_all ? dist_all + (static_cast<size_t>(b) * n + i) * k : nullptr;
-    for (int t = 0; t < k; ++t) {
-      float best_d = FLT_MAX;
-      int best_i = 0x7fffffff, best_u = 0;
-#pragma unroll
-      for (int u = 0; u < S; ++u) {
-        const int h = head[u];
-        const float dd = h < K ? md[(threadIdx.x + u) * K + h] : FLT_MAX;
-        const int ii = h < K ? mi[(threadIdx.x + u) * K + h] : 0x7fffffff;
-        if (dd < best_d || (dd == best_d && ii < best_i)) {
-          best_d = dd; best_i = ii; best_u = u;
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < S; ++u) head[u] += (u == best_u) ? 1 : 0;
-      io[t] = best_i;
-      if (dout) dout[t] = best_d;
-    }
-  }
-}
-
-// The same search with the insertion DEFERRED.  In knn_split_kernel the wave-level branch around the unrolled insertion
-// (~5 K VALU operations) is taken whenever ANY of the 64 lanes improves its list -- for 16 neighbours out of 512
-// candidates per lane that is ~95 % of all iterations, although a single lane inserts only ~70 times.  Here a lane that
-// sees a candidate below its (possibly stale, hence never too small) threshold only appends (distance, index) to a private
-// FIFO of kQueue entries in LDS; the lists are updated when some lane's FIFO is nearly full and once at the end, by
-// insertion rounds in which most lanes take part.  A lane still meets its candidates in increasing index order and the
-// insertion is the same strict `<` chain, so the result -- ties included -- is the one of knn_split_kernel, bit for bit;
-// per candidate the loop is now a distance, a compare and a predicated LDS append.  Measured (k = 16, four lanes per
-// query): 500 x 2048 x 32 shapes 200 -> 111 us, 2048 x 8192 x 32 1227 -> 691 us, 4096 x 16384 x 16 1979 -> 1251 us; a
-// 16-entry FIFO with the candidates taken four at a time (independent LDS reads and distances) against 8 entries one at a
-// time: 111 against 125 us; eight lanes per query instead of four: slower (124 / 1096 / 2029 us, more list work).  With the
-// tile as three planes + sentinels and the distances on packed fp32 operations (below): 92 / 458 / 767 us.
+// Several lanes per query, the insertion DEFERRED.  With one lane per query the kernel is one wave per SIMD at the encoder's
+// sizes (2048 queries x 32 shapes = 1024 waves) and the wave-level insertion branch fires in most iterations (any of 64 lanes
+// improving runs the unrolled shift for all): 313 us per launch whatever the batch.  Here S lanes share a query, lane s scans
+// one S-th of each LDS tile with its own sorted top-K, and the S lists are merged through LDS by (distance, index) -- the same
+// total order, S times the waves, 1/S of the iterations per wave.  Inserting at once would still take that branch (~5 K VALU
+// operations) whenever ANY of the 64 lanes improves its list -- for 16 neighbours out of 512 candidates per lane ~95 % of all
+// iterations, although a single lane inserts only ~70 times.  So a lane that sees a candidate below its (possibly stale, hence
+// never too small) threshold only appends (distance, index) to a private FIFO of kQueue entries in LDS; the lists are updated
+// when some lane's FIFO is nearly full and once at the end, by insertion rounds in which most lanes take part.  A lane still
+// meets its candidates in increasing index order and the insertion is knn_scan's strict `<` chain, so the result -- ties
+// included -- is the one of inserting at once, bit for bit; per candidate the loop is a distance, a compare and a predicated
+// LDS append.  Measured (k = 16, four lanes per query; inserting at once -> deferred): 500 x 2048 x 32 shapes 200 -> 111 us,
+// 2048 x 8192 x 32 1227 -> 691 us, 4096 x 16384 x 16 1979 -> 1251 us; a 16-entry FIFO with the candidates taken four at a time
+// (independent LDS reads and distances) against 8 entries one at a time: 111 against 125 us; eight lanes per query instead of
+// four: slower (124 / 1096 / 2029 us, more list work).  With the tile as three planes + sentinels and the distances on packed
+// fp32 operations (plane_tile.h): 92 / 458 / 767 us.
 // One workgroup's search as a function of what the two kernels below differ in: `qp` the query point of this lane's query
 // (read when `active`; the S lanes of a query pass the same), `source` the m points every lane of the workgroup searches, `io` /
 // `dout` (or NULL) the query's k output slots, and the index written = min(idx_base + index within `source`, idx_max).
@@ -234,11 +143,7 @@ __device__ __forceinline__ void knn_split_queue_scan(const float *__restrict__ q
                                                      const float *__restrict__ source, int m, int k,
                                                      int32_t *__restrict__ io, float *__restrict__ dout, int idx_base,
                                                      int idx_max) {
-  // the tile as three planes (four candidates = three 16-byte reads, two distances per packed operation) with 16 sentinel
-  // entries behind the last point: x = FLT_MAX squares to +inf, which no threshold admits -- no range checks in the scan
-  __shared__ __attribute__((aligned(16))) float tx[kTile + 16];
-  __shared__ __attribute__((aligned(16))) float ty[kTile + 16];
-  __shared__ __attribute__((aligned(16))) float tz[kTile + 16];
+  __shared__ nsdp::PlaneTile<kTile, 16> tile;      // 16 sentinel entries: no range checks in the scan
   __shared__ float md[256 * K];      // the FIFOs during the scan ([slot][thread]: conflict-free), the S lists afterwards
   __shared__ int mi[256 * K];
   static_assert(K >= kQueue, "the FIFOs live in the merge buffers");
@@ -282,13 +187,7 @@ __device__ __forceinline__ void knn_split_queue_scan(const float *__restrict__ q
   for (int base = 0; base < m; base += kTile) {
     const int cnt = min(kTile, m - base);
     __syncthreads();
-    for (int t = threadIdx.x; t < cnt; t += 256) {
-      const float *p = source + static_cast<size_t>(base + t) * 3;
-      tx[t] = p[0]; ty[t] = p[1]; tz[t] = p[2];
-    }
-    if (threadIdx.x < 16) {
-      tx[cnt + threadIdx.x] = FLT_MAX; ty[cnt + threadIdx.x] = 0.f; tz[cnt + threadIdx.x] = 0.f;
-    }
+    tile.load<256>(source + static_cast<size_t>(base) * 3, cnt);
     __syncthreads();
     // lane `sub` scans tile entries [sub * per, (sub + 1) * per), per a multiple of four (the same trip count in every
     // lane: the ballots see whole waves); S * per <= cnt + 4 S - 1: the sentinels cover what lies behind the tile.
@@ -297,21 +196,10 @@ __device__ __forceinline__ void knn_split_queue_scan(const float *__restrict__ q
     static_assert(S <= 4, "16 sentinel entries");
     for (int tt = 0; tt < per; tt += 4) {
       const int t = t0 + tt;
-      const f32x4 X = *reinterpret_cast<const f32x4 *>(&tx[t]);
-      const f32x4 Y = *reinterpret_cast<const f32x4 *>(&ty[t]);
-      const f32x4 Z = *reinterpret_cast<const f32x4 *>(&tz[t]);
-      // ((dx*dx + dy*dy) + dz*dz), dx = query - source, one rounding per operation (contraction is off in this file):
-      // nsdp::sq_dist3 on two candidates per packed instruction
-      const f32x2 q2x = {qx, qx}, q2y = {qy, qy}, q2z = {qz, qz};
-      f32x2 d01, d23;
-      {
-        const f32x2 dx = q2x - f32x2{X[0], X[1]}, dy = q2y - f32x2{Y[0], Y[1]}, dz = q2z - f32x2{Z[0], Z[1]};
-        d01 = (dx * dx + dy * dy) + dz * dz;
-      }
-      {
-        const f32x2 dx = q2x - f32x2{X[2], X[3]}, dy = q2y - f32x2{Y[2], Y[3]}, dz = q2z - f32x2{Z[2], Z[3]};
-        d23 = (dx * dx + dy * dy) + dz * dz;
-      }
+      nsdp::f32x4 X, Y, Z;
+      nsdp::f32x2 d01, d23;
+      tile.read4(t, X, Y, Z);
+      nsdp::dist4(X, Y, Z, qx, qy, qz, d01, d23);
       const float d[4] = {d01[0], d01[1], d23[0], d23[1]};
       const float thr = bd[K - 1];
 #pragma unroll
@@ -427,9 +315,6 @@ __global__ __launch_bounds__(256) void knn_rs_kernel(const float *__restrict__ q
               dist_all ? dist_all + row * k : nullptr, lo, cap - 1);
 }
 
-
-int g_knn_queue = 1;      // nsdp_debug_set(10, v), NSDP_KNN_QUEUE: 0 = the immediate-insertion kernel (A/B)
-
 template <int K>
 int launch(const float *q, const float *s, int B, int n, int m, int k, int32_t *idx, float *d2,
            hipStream_t st) {
@@ -439,15 +324,10 @@ int launch(const float *q, const float *s, int B, int n, int m, int k, int32_t *
   if constexpr (K <= 16) {
     if (m >= 256 && waves < 8LL * nsdp::num_cus()) {
       dim3 grid(nsdp::ceil_div(n, 64), B);
-      if (g_knn_queue) {
-        constexpr int kQueue = K >= 16 ? 16 : 8;
-        NSDP_TRACE("knn_split_queue<%d,4,%d>", K, kQueue);
-        hipLaunchKernelGGL((knn_split_queue_kernel<K, 4, kQueue>), grid, dim3(256), 0, st, q, s, n, m, k, idx, d2);
-        return nsdp::launch_status("knn_split_queue_kernel");
-      }
-      NSDP_TRACE("knn_split<%d,4>", K);
-      hipLaunchKernelGGL((knn_split_kernel<K, 4>), grid, dim3(256), 0, st, q, s, n, m, k, idx, d2);
-      return nsdp::launch_status("knn_split_kernel");
+      constexpr int kQueue = K >= 16 ? 16 : 8;
+      NSDP_TRACE("knn_split_queue<%d,4,%d>", K, kQueue);
+      hipLaunchKernelGGL((knn_split_queue_kernel<K, 4, kQueue>), grid, dim3(256), 0, st, q, s, n, m, k, idx, d2);
+      return nsdp::launch_status("knn_split_queue_kernel");
     }
   }
   dim3 grid(nsdp::ceil_div(n, 256), B);
@@ -487,11 +367,17 @@ int launch_rs(const float *q, const int32_t *qoff, const float *s, const int32_t
   return nsdp::launch_status("knn_rs_kernel");
 }
 
-}  // namespace
+// the kernels keep K list entries in registers: f(std::integral_constant<int, K>) for the smallest instantiated K >= k (the
+// entries have checked k <= 64)
+template <class F>
+int with_list_size(int k, F &&f) {
+  if (k <= 8) return f(std::integral_constant<int, 8>{});
+  if (k <= 16) return f(std::integral_constant<int, 16>{});
+  if (k <= 32) return f(std::integral_constant<int, 32>{});
+  return f(std::integral_constant<int, 64>{});
+}
 
-namespace nsdp {
-void debug_set_knn(int value) { g_knn_queue = value; }
-}  // namespace nsdp
+}  // namespace
 
 extern "C" int nsdp_knn(const float *query, const float *source, int B, int n, int m, int k,
                         int32_t *idx_out, float *dist2_out, void *stream) {
@@ -503,10 +389,7 @@ extern "C" int nsdp_knn(const float *query, const float *source, int B, int n, i
   hipStream_t st = nsdp::as_stream(stream);
   nsdp::prof::Scope scope(nsdp::prof::kKnn, st, 0.0,
                           static_cast<double>(B) * (12.0 * (n + m) + 4.0 * n * k * (dist2_out ? 2 : 1)));
-  if (k <= 8) return launch<8>(query, source, B, n, m, k, idx_out, dist2_out, st);
-  if (k <= 16) return launch<16>(query, source, B, n, m, k, idx_out, dist2_out, st);
-  if (k <= 32) return launch<32>(query, source, B, n, m, k, idx_out, dist2_out, st);
-  return launch<64>(query, source, B, n, m, k, idx_out, dist2_out, st);
+  return with_list_size(k, [&](auto K) { return launch<K>(query, source, B, n, m, k, idx_out, dist2_out, st); });
 }
 
 extern "C" int nsdp_knn_ragged(const float *query, const int32_t *offsets, const float *source, int B, int cap, int m,
@@ -521,10 +404,7 @@ extern "C" int nsdp_knn_ragged(const float *query, const int32_t *offsets, const
   nsdp::prof::Scope scope(nsdp::prof::kKnn, st, 0.0,
                           12.0 * (static_cast<double>(cap) + static_cast<double>(B) * m) +
                               4.0 * cap * k * (dist2_out ? 2 : 1));
-  if (k <= 8) return launch_ragged<8>(query, offsets, source, B, cap, m, k, idx_out, dist2_out, st);
-  if (k <= 16) return launch_ragged<16>(query, offsets, source, B, cap, m, k, idx_out, dist2_out, st);
-  if (k <= 32) return launch_ragged<32>(query, offsets, source, B, cap, m, k, idx_out, dist2_out, st);
-  return launch_ragged<64>(query, offsets, source, B, cap, m, k, idx_out, dist2_out, st);
+  return with_list_size(k, [&](auto K) { return launch_ragged<K>(query, offsets, source, B, cap, m, k, idx_out, dist2_out, st); });
 }
 
 extern "C" int nsdp_knn_ragged_source(const float *query, const int32_t *query_offsets, const float *source,
@@ -541,8 +421,7 @@ extern "C" int nsdp_knn_ragged_source(const float *query, const int32_t *query_o
   hipStream_t st = nsdp::as_stream(stream);
   nsdp::prof::Scope scope(nsdp::prof::kKnn, st, 0.0,
                           12.0 * (static_cast<double>(rows) + cap) + 4.0 * rows * k * (dist2_out ? 2 : 1));
-  if (k <= 8) return launch_rs<8>(query, query_offsets, source, offsets, B, n, qcap, cap, n_max, k, idx_out, dist2_out, st);
-  if (k <= 16) return launch_rs<16>(query, query_offsets, source, offsets, B, n, qcap, cap, n_max, k, idx_out, dist2_out, st);
-  if (k <= 32) return launch_rs<32>(query, query_offsets, source, offsets, B, n, qcap, cap, n_max, k, idx_out, dist2_out, st);
-  return launch_rs<64>(query, query_offsets, source, offsets, B, n, qcap, cap, n_max, k, idx_out, dist2_out, st);
+  return with_list_size(k, [&](auto K) {
+    return launch_rs<K>(query, query_offsets, source, offsets, B, n, qcap, cap, n_max, k, idx_out, dist2_out, st);
+  });
 }

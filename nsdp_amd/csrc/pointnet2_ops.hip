@@ -9,6 +9,7 @@
 #include <cfloat>
 
 #include "common.h"
+#include "plane_tile.h"
 #include "prof.h"
 
 #pragma clang fp contract(off)
@@ -507,7 +508,8 @@ int launch_scatter_cm(const float *grad_out, const int32_t *idx, int B, int C, i
 constexpr int kSrcTile = 1024;
 
 // ball_query_gpu.cu:9-44: first `nsample` indices (in index order) with d2 < r^2; the first hit also
-// pre-fills every slot; no hit leaves zeros (output is zero-filled before the launch).
+// pre-fills every slot; no hit leaves zeros (output is zero-filled before the launch).  One lane per query: the only form for
+// nsample > kBallMaxSample, the LDS output rows of ball_query_quad_kernel below.
 __global__ __launch_bounds__(kThreads) void ball_query_kernel(
     const float *__restrict__ new_xyz_all, const float *__restrict__ xyz_all, int N, int M,
     float radius2, int nsample, int32_t *__restrict__ idx_all) {
@@ -545,111 +547,24 @@ __global__ __launch_bounds__(kThreads) void ball_query_kernel(
   }
 }
 
-// interpolate_gpu.cu:9-59: three nearest `known` points per `unknown` point, bests kept in double.
-__global__ __launch_bounds__(kThreads) void three_nn_kernel(const float *__restrict__ unknown_all,
-                                                            const float *__restrict__ known_all, int n,
-                                                            int m, float *__restrict__ dist2_all,
-                                                            int32_t *__restrict__ idx_all) {
-  __shared__ float4 tile[kSrcTile];
-  const int b = blockIdx.y;
-  const float *known = known_all + static_cast<size_t>(b) * m * 3;
-  const int j = blockIdx.x * kThreads + threadIdx.x;
-  const bool active = j < n;
-  float ux = 0.f, uy = 0.f, uz = 0.f;
-  if (active) {
-    const float *u = unknown_all + (static_cast<size_t>(b) * n + j) * 3;
-    ux = u[0]; uy = u[1]; uz = u[2];
-  }
-  double best1 = 1e40, best2 = 1e40, best3 = 1e40;
-  int besti1 = 0, besti2 = 0, besti3 = 0;
-  for (int base = 0; base < m; base += kSrcTile) {
-    const int n_tile = min(kSrcTile, m - base);
-    __syncthreads();
-    for (int t = threadIdx.x; t < n_tile; t += kThreads) {
-      const float *p = known + static_cast<size_t>(base + t) * 3;
-      tile[t] = make_float4(p[0], p[1], p[2], 0.f);
-    }
-    __syncthreads();
-    for (int t = 0; t < n_tile; ++t) {
-      const float4 s = tile[t];
-      const double d = static_cast<double>(nsdp::sq_dist3(ux, uy, uz, s.x, s.y, s.z));
-      const int k = base + t;
-      if (d < best1) {
-        best3 = best2; besti3 = besti2;
-        best2 = best1; besti2 = besti1;
-        best1 = d; besti1 = k;
-      } else if (d < best2) {
-        best3 = best2; besti3 = besti2;
-        best2 = d; besti2 = k;
-      } else if (d < best3) {
-        best3 = d; besti3 = k;
-      }
-    }
-  }
-  if (active) {
-    float *d2 = dist2_all + (static_cast<size_t>(b) * n + j) * 3;
-    int32_t *io = idx_all + (static_cast<size_t>(b) * n + j) * 3;
-    d2[0] = static_cast<float>(best1); d2[1] = static_cast<float>(best2); d2[2] = static_cast<float>(best3);
-    io[0] = besti1; io[1] = besti2; io[2] = besti3;
-  }
-}
-
 // ---------------------------------------------------------------------------------------------------------------------------
-// The two searches above with the scan of csrc/knn.hip (knn_split_queue_kernel): the source tile as three coordinate planes
-// with 16 sentinel entries behind the last point (x = FLT_MAX squares to +inf, which neither `d < r^2` nor `d < best` admits:
-// no range checks), FOUR lanes per query -- a quad walks the tile 16 candidates at a time, lane `sub` takes candidates
-// 4 sub .. 4 sub + 3 of every group (one 64-byte LDS read per quad and plane, the same for all 16 quads of a wave: a
-// broadcast) -- and the distances two at a time on packed fp32 operations, still ((dx*dx + dy*dy) + dz*dz) with one rounding
-// per operation (contraction is off in this file).  With one lane per query (the kernels above) the encoder-sized problems
-// are one wave per SIMD and the scan is latency-bound: 0.04-0.18 of the VALU peak in distance tests (profiles/r4_grouping.txt).
-// Results are bit-identical to the one-lane kernels (tests/test_geometry_gpu.py holds both to the CPU checker); nsdp_debug_set(12, 0)
-// switches back (A/B).
+// ball_query and three_nn (interpolate_gpu.cu:9-59: the three nearest `known` points per `unknown` point) with the scan of
+// csrc/knn.hip (knn_split_queue_kernel): the source tile of plane_tile.h with 16 sentinel entries (neither `d < r^2` nor
+// `d < best` admits one: no range checks), FOUR lanes per query -- a quad walks the tile 16 candidates at a time, lane `sub`
+// takes candidates 4 sub .. 4 sub + 3 of every group (one 64-byte LDS read per quad and plane, the same for all 16 quads of a
+// wave: a broadcast) -- and the distances by plane_tile.h's dist4, the bits of nsdp::sq_dist3.  With one lane per query the
+// encoder-sized problems are one wave per SIMD and the scan is latency-bound: 0.04-0.18 of the VALU peak in distance tests
+// (profiles/r4_grouping.txt).  tests/test_geometry_gpu.py holds the results to the CPU checker bit for bit.
 // ---------------------------------------------------------------------------------------------------------------------------
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
 constexpr int kQuad = 4;
 constexpr int kQuadQueries = kThreads / kQuad;      // queries per workgroup
 constexpr int kBallMaxSample = 64;                  // the LDS output rows of ball_query_quad_kernel
-
-struct PlaneTile {
-  __attribute__((aligned(16))) float x[kSrcTile + 16];
-  __attribute__((aligned(16))) float y[kSrcTile + 16];
-  __attribute__((aligned(16))) float z[kSrcTile + 16];
-};
-
-// (the caller has a barrier in front: nobody reads the previous tile any more)
-__device__ __forceinline__ void load_plane_tile(PlaneTile &t, const float *__restrict__ src, int cnt) {
-  for (int i = threadIdx.x; i < cnt; i += kThreads) {
-    const float *p = src + static_cast<size_t>(i) * 3;
-    t.x[i] = p[0]; t.y[i] = p[1]; t.z[i] = p[2];
-  }
-  if (threadIdx.x < 16) {
-    t.x[cnt + threadIdx.x] = FLT_MAX; t.y[cnt + threadIdx.x] = 0.f; t.z[cnt + threadIdx.x] = 0.f;
-  }
-}
-
-// squared distances of the query to candidates i .. i + 3 of the tile (i % 4 == 0)
-__device__ __forceinline__ void dist4(const PlaneTile &t, int i, float qx, float qy, float qz, float (&d)[4]) {
-  const f32x4_t X = *reinterpret_cast<const f32x4_t *>(&t.x[i]);
-  const f32x4_t Y = *reinterpret_cast<const f32x4_t *>(&t.y[i]);
-  const f32x4_t Z = *reinterpret_cast<const f32x4_t *>(&t.z[i]);
-  const f32x2_t q2x = {qx, qx}, q2y = {qy, qy}, q2z = {qz, qz};
-  {
-    const f32x2_t dx = q2x - f32x2_t{X[0], X[1]}, dy = q2y - f32x2_t{Y[0], Y[1]}, dz = q2z - f32x2_t{Z[0], Z[1]};
-    const f32x2_t r = (dx * dx + dy * dy) + dz * dz;
-    d[0] = r[0]; d[1] = r[1];
-  }
-  {
-    const f32x2_t dx = q2x - f32x2_t{X[2], X[3]}, dy = q2y - f32x2_t{Y[2], Y[3]}, dz = q2z - f32x2_t{Z[2], Z[3]};
-    const f32x2_t r = (dx * dx + dy * dy) + dz * dz;
-    d[2] = r[0]; d[3] = r[1];
-  }
-}
+using SearchTile = nsdp::PlaneTile<kSrcTile, 16>;
 
 __global__ __launch_bounds__(kThreads) void ball_query_quad_kernel(const float *__restrict__ new_xyz_all,
                                                                   const float *__restrict__ xyz_all, int N, int M, float radius2,
                                                                   int nsample, int32_t *__restrict__ idx_all) {
-  __shared__ PlaneTile tile;
+  __shared__ SearchTile tile;
   __shared__ int32_t obuf[kQuadQueries * kBallMaxSample];      // [query][nsample]: written out in one contiguous run
   const int b = blockIdx.y;
   const float *xyz = xyz_all + static_cast<size_t>(b) * N * 3;
@@ -667,14 +582,17 @@ __global__ __launch_bounds__(kThreads) void ball_query_quad_kernel(const float *
   for (int base = 0; base < N; base += kSrcTile) {
     if (__syncthreads_and(cnt >= nsample)) break;          // (a barrier: the previous tile is no longer read)
     const int n_tile = min(kSrcTile, N - base);
-    load_plane_tile(tile, xyz + static_cast<size_t>(base) * 3, n_tile);
+    tile.load<kThreads>(xyz + static_cast<size_t>(base) * 3, n_tile);
     __syncthreads();
     const int steps = (n_tile + 15) >> 4;
     for (int s = 0; s < steps; ++s) {
       if (__builtin_amdgcn_ballot_w64(cnt < nsample) == 0) break;
       const int t = 16 * s + 4 * sub;
-      float d[4];
-      dist4(tile, t, qx, qy, qz, d);
+      nsdp::f32x4 X, Y, Z;
+      nsdp::f32x2 d01, d23;
+      tile.read4(t, X, Y, Z);
+      nsdp::dist4(X, Y, Z, qx, qy, qz, d01, d23);
+      const float d[4] = {d01[0], d01[1], d23[0], d23[1]};
       const unsigned mask = (d[0] < radius2 ? 1u : 0u) | (d[1] < radius2 ? 2u : 0u) | (d[2] < radius2 ? 4u : 0u) |
                             (d[3] < radius2 ? 8u : 0u);
       if (__builtin_amdgcn_ballot_w64(mask != 0) == 0) continue;
@@ -714,7 +632,7 @@ __global__ __launch_bounds__(kThreads) void ball_query_quad_kernel(const float *
 __global__ __launch_bounds__(kThreads) void three_nn_quad_kernel(const float *__restrict__ unknown_all,
                                                                 const float *__restrict__ known_all, int n, int m,
                                                                 float *__restrict__ dist2_all, int32_t *__restrict__ idx_all) {
-  __shared__ PlaneTile tile;
+  __shared__ SearchTile tile;
   const int b = blockIdx.y;
   const float *known = known_all + static_cast<size_t>(b) * m * 3;
   const int ql = threadIdx.x / kQuad, sub = threadIdx.x % kQuad;
@@ -733,13 +651,16 @@ __global__ __launch_bounds__(kThreads) void three_nn_quad_kernel(const float *__
   for (int base = 0; base < m; base += kSrcTile) {
     const int n_tile = min(kSrcTile, m - base);
     __syncthreads();
-    load_plane_tile(tile, known + static_cast<size_t>(base) * 3, n_tile);
+    tile.load<kThreads>(known + static_cast<size_t>(base) * 3, n_tile);
     __syncthreads();
     const int steps = (n_tile + 15) >> 4;
     for (int s = 0; s < steps; ++s) {
       const int t = 16 * s + 4 * sub;
-      float d[4];
-      dist4(tile, t, ux, uy, uz, d);
+      nsdp::f32x4 X, Y, Z;
+      nsdp::f32x2 d01, d23;
+      tile.read4(t, X, Y, Z);
+      nsdp::dist4(X, Y, Z, ux, uy, uz, d01, d23);
+      const float d[4] = {d01[0], d01[1], d23[0], d23[1]};
       const bool any = d[0] < b3 || d[1] < b3 || d[2] < b3 || d[3] < b3;
       if (__builtin_amdgcn_ballot_w64(any) == 0) continue;
 #pragma unroll
@@ -805,8 +726,6 @@ __global__ __launch_bounds__(kThreads) void rel_coords4_kernel(const float *__re
     out[e] = make_float4(dx, dy, dz, 0.f);
   }
 }
-
-int g_search_quad = 1;      // nsdp_debug_set(12, v), NSDP_SEARCH_QUAD: 0 = the one-lane-per-query kernels (A/B)
 
 // out[b,l,j] = sum_t points[b,l,idx[b,j,t]] * weight[b,j,t]  (interpolate_gpu.cu:72-101), LDS-staged like the gathers:
 // a workgroup owns CH whole (b, l) rows of m floats; a thread owns one j at a time -- its three indices and weights are
@@ -952,10 +871,6 @@ __global__ void scatter_add_rows_kernel(const float *__restrict__ grad_out,
 
 }  // namespace
 
-namespace nsdp {
-void debug_set_search(int value) { g_search_quad = value; }
-}  // namespace nsdp
-
 extern "C" {
 
 int nsdp_gather_points(const float *points, const int32_t *idx, int B, int C, int N, int M, float *out,
@@ -1024,7 +939,7 @@ int nsdp_ball_query(const float *new_xyz, const float *xyz, int B, int N, int M,
   NSDP_REQUIRE(B <= 65535, "ball_query: batch %d too large", B);
   hipStream_t st = nsdp::as_stream(stream);
   const float radius2 = radius * radius;
-  if (g_search_quad && nsample <= kBallMaxSample) {      // (writes every slot itself: no memset in front)
+  if (nsample <= kBallMaxSample) {      // (writes every slot itself: no memset in front)
     NSDP_TRACE("ball_query_quad");
     hipLaunchKernelGGL(ball_query_quad_kernel, dim3(nsdp::ceil_div(M, kQuadQueries), B), dim3(kThreads), 0, st, new_xyz, xyz, N,
                        M, radius2, nsample, idx_out);
@@ -1042,16 +957,10 @@ int nsdp_three_nn(const float *unknown, const float *known, int B, int n, int m,
   if (static_cast<long long>(B) * n <= 0) return 0;
   NSDP_REQUIRE(unknown && dist2 && idx && (known || m == 0), "three_nn: null pointer");
   NSDP_REQUIRE(B <= 65535, "three_nn: batch %d too large", B);
-  if (g_search_quad) {
-    NSDP_TRACE("three_nn_quad");
-    hipLaunchKernelGGL(three_nn_quad_kernel, dim3(nsdp::ceil_div(n, kQuadQueries), B), dim3(kThreads), 0,
-                       nsdp::as_stream(stream), unknown, known, n, m, dist2, idx);
-    return nsdp::launch_status("three_nn_quad_kernel");
-  }
-  NSDP_TRACE("three_nn");
-  hipLaunchKernelGGL(three_nn_kernel, dim3(nsdp::ceil_div(n, kThreads), B), dim3(kThreads), 0,
+  NSDP_TRACE("three_nn_quad");
+  hipLaunchKernelGGL(three_nn_quad_kernel, dim3(nsdp::ceil_div(n, kQuadQueries), B), dim3(kThreads), 0,
                      nsdp::as_stream(stream), unknown, known, n, m, dist2, idx);
-  return nsdp::launch_status("three_nn_kernel");
+  return nsdp::launch_status("three_nn_quad_kernel");
 }
 
 int nsdp_three_interpolate(const float *points, const int32_t *idx, const float *weight, int B, int c,

@@ -84,34 +84,29 @@ def test_knn_ties_follow_distance_then_index():
 
 
 @pytest.mark.parametrize("kind,b,n,m,k", [("uniform", 3, 2048, 2048, 16), ("dupes", 2, 500, 2048, 16), ("grid", 2, 512, 512, 16),
-                                          ("uniform", 2, 300, 5000, 16), ("allorigin", 2, 300, 700, 9), ("uniform", 2, 257, 1025, 5)])
-def test_knn_deferred_insertion_equals_immediate_insertion(kind, b, n, m, k):
-    """knn_split_queue_kernel (candidates appended to per-lane FIFOs, lists updated in rounds) is the default of the
-    several-lanes-per-query search; knn_split_kernel (insert at once) stays as its A/B form.  Same candidate order per lane,
-    same strict `<` chain: indices and distance bits must be equal on ties, duplicates, ragged tiles and all."""
+                                          ("uniform", 2, 300, 5000, 16), ("allorigin", 2, 300, 700, 9), ("uniform", 2, 257, 1025, 5),
+                                          # the sentinel edge of the plane tile: the smallest source that takes the split form; a
+                                          # last tile of 3 rows (every lane's quarter ends in sentinels)
+                                          ("uniform", 2, 65, 256, 16), ("dupes", 2, 65, 1027, 8)])
+def test_knn_split_queue_matches_oracle(kind, b, n, m, k):
+    """knn_split_queue_kernel (several lanes per query, candidates appended to per-lane FIFOs, lists updated in rounds, the
+    lanes' lists merged by (distance, index)) against the CPU checker, which orders by distance then index: indices and
+    distance bits must be equal on ties, duplicates, ragged tiles and all."""
     from test_model_gpu import _variant_trace
-    from nsdp_amd import _lib
     from nsdp_amd import pointnet2_utils as pu
     s = _cloud(11 * n + m, b, m, kind)
     q = s[:, :n].copy() if n <= m else _cloud(n, b, n, kind)
-    out = {}
-    for mode in (0, 1):
-        _lib.lib().nsdp_debug_set(10, mode)
-        try:
-            with _variant_trace() as names:
-                idx, d2 = pu.knn(_dev(q), _dev(s), k, return_dist=True)
-                torch.cuda.synchronize()
-        finally:
-            _lib.lib().nsdp_debug_set(10, int(os.environ.get("NSDP_KNN_QUEUE", "1")))
-        assert any(x.startswith("knn_split_queue<" if mode else "knn_split<") for x in names), names
-        out[mode] = (idx.cpu().numpy(), d2.cpu().numpy().view(np.uint32))
-    np.testing.assert_array_equal(out[0][0], out[1][0])
-    np.testing.assert_array_equal(out[0][1], out[1][1])
-    ridx = ref.knn(q, s, k)
-    if kind != "allorigin":        # (all distances equal: the oracle's order is distance-then-index as well, checked below)
-        np.testing.assert_array_equal(out[1][0], ridx)
-    else:
-        np.testing.assert_array_equal(out[1][0], np.tile(np.arange(k, dtype=np.int32), (b, n, 1)))
+    with _variant_trace() as names:
+        idx, d2 = pu.knn(_dev(q), _dev(s), k, return_dist=True)
+        torch.cuda.synchronize()
+    assert any(x.startswith("knn_split_queue<") for x in names), names
+    idx, d2 = idx.cpu().numpy(), d2.cpu().numpy().view(np.uint32)
+    ridx, rd2 = ref.knn(q, s, k, return_dist=True)
+    np.testing.assert_array_equal(idx, ridx)
+    np.testing.assert_array_equal(d2, rd2.view(np.uint32))
+    if kind == "allorigin":        # (all distances equal: the order is the index order, stated here independently of the checker)
+        np.testing.assert_array_equal(idx, np.tile(np.arange(k, dtype=np.int32), (b, n, 1)))
+        assert not d2.any()
 
 
 def test_knn_golden_sets(golden_dir):
@@ -236,8 +231,7 @@ def test_ball_query_four_lane_scan_matches_oracle(kind, B, N, M, radius, nsample
         new_xyz = _cloud(200 + M, B, M)
     got, names = _trace_names(lambda: pu.ball_query(radius, nsample, _dev(xyz), _dev(new_xyz)))
     np.testing.assert_array_equal(got.cpu().numpy(), ref.ball_query(new_xyz, xyz, radius, nsample))
-    if os.environ.get("NSDP_SEARCH_QUAD", "1") != "0":
-        assert ("ball_query_quad" in names) == (nsample <= 64), names
+    assert ("ball_query_quad" in names) == (nsample <= 64), names
 
 
 @pytest.mark.parametrize("kind", ["uniform", "dupes", "grid"])
@@ -262,8 +256,7 @@ def test_three_nn_four_lane_scan_matches_oracle(kind, B, n, m):
     rd2, ridx = ref.three_nn(unknown, known)
     np.testing.assert_array_equal(idx.cpu().numpy(), ridx)
     np.testing.assert_array_equal(d2.cpu().numpy(), rd2)
-    if os.environ.get("NSDP_SEARCH_QUAD", "1") != "0":
-        assert "three_nn_quad" in names, names
+    assert "three_nn_quad" in names, names
 
 
 @pytest.mark.parametrize("B,n,m,k,sign", [(2, 300, 1000, 16, 1.0), (3, 100, 100, 100, 1.0), (2, 64, 500, 7, -1.0), (1, 1, 5, 3, -1.0)])
