@@ -347,7 +347,9 @@ int nsdp_linear_wgrad_bf16x3_f32(const float *dY, const float *X, const float *m
  *                       until the reduce; *desc_out describes the pending reduction (workspace, targets, partial count, tiles)
  *   _reduce_batched     dW (+)= the fixed-order sum of the partials, db likewise, for `count` descriptors (host array, copied
  *                       into the kernel arguments, 48 per launch).  The sums are those of nsdp_linear_wgrad_bf16x3_f32, bit for
- *                       bit.  Two descriptors of one launch must not share a target (`accumulate` reads what is there). */
+ *                       bit: both run the one body of csrc/wgrad_reduce.h, whose head states the summation order (eight
+ *                       ranges of four chains over the fragment-ordered partials; tests/wgrad_reduce_ref.py emulates it).
+ *                       Two descriptors of one launch must not share a target (`accumulate` reads what is there). */
 typedef struct {
   const float *ws;
   float *dW, *db;      /* db may be NULL */
@@ -454,7 +456,8 @@ int nsdp_linear_wgrad_bf16_partials(const void *dY, const void *X, const void *m
                                     NsdpWgradB16ReduceDesc *desc_out, void *stream);
 int nsdp_wgrad_bf16_reduce_batched(const NsdpWgradB16ReduceDesc *descs, int count, void *stream);
 /* nsdp_linear_wgrad_f32 (the exact-fp32 kernels of the small layers) likewise: its partials have the same [S][N K + N] layout,
- * its reduce the same eight chains -- the descriptor goes to nsdp_wgrad_bf16_reduce_batched. */
+ * its reduce the same eight chains (the linear layout of csrc/wgrad_reduce.h: one kernel behind both one-call forms and the
+ * batched entry) -- the descriptor goes to nsdp_wgrad_bf16_reduce_batched. */
 int nsdp_linear_wgrad_partials_f32(const float *dY, const float *X, const float *mask, int relu_x, float *dW, float *db,
                                    long long M, int N, int K, int accumulate, float *workspace, size_t workspace_bytes,
                                    NsdpWgradB16ReduceDesc *desc_out, void *stream);

@@ -16,9 +16,7 @@
 // Weights: [out tile][k block][lane = 16 g + li][8] bf16 (1 KiB per block), the half block [lane][4] (512 B) last, so one out
 // tile is NTIN * 512 bytes.
 
-using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
-using u32x2 = __attribute__((ext_vector_type(2))) unsigned;
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
+using u32x2 = __attribute__((ext_vector_type(2))) unsigned;      // (u32x4, bf16x8: mfma_util.h, through chain_f32.h)
 using s16x4 = __attribute__((ext_vector_type(4))) short;
 
 #ifndef NSDP_DEC16_PREFETCH

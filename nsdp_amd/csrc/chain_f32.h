@@ -2,9 +2,9 @@
 // the training-mode forward of the cross attention): one wave, 16 rows, Y^T = W X^T on v_mfma_f32_16x16x4_f32 with the
 // accumulator layout of layer L being the B-operand layout of layer L + 1, fragment-major weights prefetched through a
 // register ring by hand-issued loads.  Included into the anonymous namespace of both translation units.
-// (no include guard and no #include here: the including translation unit pulls in <type_traits> at global scope first)
-
-using f32x4 = __attribute__((ext_vector_type(4))) float;
+// (no include guard; the including translation unit pulls in <type_traits> at global scope first, so that mfma_util.h -- f32x4,
+// static_for -- adds nothing but its own names here)
+#include "mfma_util.h"
 
 // v_out[ot] = act( W[ot*16 + ., :] * v_in + bias )  for NTOUT output tiles, NTIN input tiles.
 // W row-major [NTOUT*16, NTIN*16] (zero padded); ACC: v_out is also the start value (fused residual add).
@@ -24,14 +24,6 @@ using f32x4 = __attribute__((ext_vector_type(4))) float;
 #endif
 constexpr int kPrefetch = NSDP_DEC_PREFETCH;
 constexpr int kRing = 8;
-
-template <int I, int N, typename F>
-__device__ __forceinline__ void static_for(F &&f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>{});
-    static_for<I + 1, N>(f);
-  }
-}
 
 __device__ __forceinline__ float4 ldg4(const float *uniform_base, unsigned lane_byte_off) {
   return *reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(uniform_base) + lane_byte_off);

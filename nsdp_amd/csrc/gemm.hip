@@ -24,10 +24,9 @@
 #include "k4.h"
 #include "pack_bodies.h"
 #include "prof.h"
+#include "wgrad_reduce.h"
 
 namespace {
-
-using f32x4 = __attribute__((ext_vector_type(4))) float;
 
 int g_nt_dbg = 0;
 int g_nt_pipe = 1;  // nsdp_debug_set(3, v): 1 = fenced two-buffer software pipeline, 0 = register-lean loop
@@ -952,7 +951,7 @@ void dispatch_wgrad_k(const WgradParams &p, unsigned chunks, int ktiles, hipStre
 // float -- nothing for the matrix pipe, a pure stream over dY (and its ReLU mask).  N/4 lanes per row read the row as
 // float4 (fully coalesced, 4 rows in flight per lane), each lane keeps the 4 x 4 products of its four channels and
 // their column sums; the row slots of a workgroup are combined through LDS in fixed order and written as one partial
-// in the layout of reduce_partials_kernel.  The MFMA kernel it replaces here ran at 2.9 TB/s with a quarter of its
+// in the linear layout of wgrad_reduce.h.  The MFMA kernel it replaces here ran at 2.9 TB/s with a quarter of its
 // tile rows padding.
 // MASK: 0 none, 1 dY *= (mask > 0) with mask [M, N] read from memory, 2 the same mask RECOMPUTED from the layer's input
 // rows (already loaded: they are the X operand) and its weights: relu'(x W0^T + b0), bit for bit the forward kernel's
@@ -1035,27 +1034,6 @@ __global__ __launch_bounds__(256) void linear_wgrad_k4_kernel(WgradParams p) {
     for (int u = 0; u < slots; ++u) s += red[u * lpr + q][v];
     if (v < 16) out[(4 * q + (v >> 2)) * 4 + (v & 3)] = s;            // dW[n][k], n = 4 q + v / 4
     else if (p.want_db) out[static_cast<long long>(N) * 4 + 4 * q + (v - 16)] = s;
-  }
-}
-
-__global__ void reduce_partials_kernel(const float *__restrict__ ws, int S, long long stride,
-                                       long long nw, float *__restrict__ dW, long long nb,
-                                       float *__restrict__ db, int accumulate) {
-  const long long e = blockIdx.x * 256LL + threadIdx.x;
-  if (e >= nw + nb) return;
-  // 8 independent partial sums keep 8 loads in flight per lane (a single dependent chain is latency-bound)
-  float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  int c = 0;
-  for (; c + 8 <= S; c += 8) {
-#pragma unroll
-    for (int u = 0; u < 8; ++u) acc[u] += ws[(c + u) * stride + e];
-  }
-  for (; c < S; ++c) acc[0] += ws[c * stride + e];
-  const float s = ((acc[0] + acc[1]) + (acc[2] + acc[3])) + ((acc[4] + acc[5]) + (acc[6] + acc[7]));
-  if (e < nw) {
-    dW[e] = accumulate ? dW[e] + s : s;
-  } else if (db) {
-    db[e - nw] = accumulate ? db[e - nw] + s : s;
   }
 }
 
@@ -1290,15 +1268,13 @@ static int wgrad_f32_impl(const float *dY, const float *X, const float *mask, co
     int rc = nsdp::launch_status("linear_wgrad_kernel");
     if (rc) return rc;
   }
-  if (desc_out) {      // the caller sums these partials with a batch: same layout ([slots][N K + N]) and the same eight chains
-    *desc_out = NsdpWgradB16ReduceDesc{workspace, dW, db, static_cast<int>(pl.slots), N, K, accumulate ? 1 : 0, 0};
+  // the partials [slots][N K + N] and their sum (wgrad_reduce.h, linear layout): handed to the caller's batch, or reduced here
+  const NsdpWgradB16ReduceDesc desc{workspace, dW, db, static_cast<int>(pl.slots), N, K, accumulate ? 1 : 0, 0};
+  if (desc_out) {
+    *desc_out = desc;
     return 0;
   }
-  const long long nw = static_cast<long long>(N) * K;
-  hipLaunchKernelGGL(reduce_partials_kernel, dim3(static_cast<unsigned>((nw + N + 255) / 256)), dim3(256), 0,
-                     st, workspace, static_cast<int>(pl.slots), nw + N, nw, dW, static_cast<long long>(N), db,
-                     accumulate);
-  return nsdp::launch_status("reduce_partials_kernel");
+  return reduce_one(desc, st);
 }
 
 int nsdp_linear_wgrad_f32(const float *dY, const float *X, const float *mask, int relu_x, float *dW,

@@ -23,16 +23,13 @@
 #include <type_traits>
 
 #include "common.h"
+#include "mfma_util.h"
 #include "prof.h"
+#include "wgrad_reduce.h"
 
 namespace {
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-using f32x2 = __attribute__((ext_vector_type(2))) float;
-using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
 using u32x2 = __attribute__((ext_vector_type(2))) unsigned;
-using bf16x2 = __attribute__((ext_vector_type(2))) __bf16;
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
 
 __device__ __forceinline__ unsigned pack2(float a, float b) {   // (lo = a, hi = b), round to nearest even
   return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{a, b}, bf16x2));
@@ -49,10 +46,6 @@ __device__ __forceinline__ unsigned relu2(unsigned v) {        // max(x, 0) on b
   const unsigned lo = (v & 0x00008000u) ? 0u : 0x0000ffffu;
   const unsigned hi = (v & 0x80000000u) ? 0u : 0xffff0000u;
   return v & (lo | hi);
-}
-
-__device__ __forceinline__ f32x4 mfma_bf16(u32x4 a, u32x4 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
 }
 
 // output channel of MFMA row i of n tile nt (NT tiles in all): tiles are paired so that a lane's 2 x 4 accumulator
@@ -609,64 +602,13 @@ __global__ __launch_bounds__(kWavesWg * 64, 1) void wgrad_bf16_kernel(Wg16Params
   }
 }
 
-// dst[e] (+)= sum over the S partials, fixed order, 8 independent chains
-__global__ __launch_bounds__(256) void reduce_b16_kernel(const float *__restrict__ ws, int S, long long stride,
-                                                         long long nw, float *__restrict__ dW, long long nb,
-                                                         float *__restrict__ db, int accumulate) {
-  const long long e = blockIdx.x * 256LL + threadIdx.x;
-  if (e >= nw + nb) return;
-  float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  int c = 0;
-  for (; c + 8 <= S; c += 8) {
-#pragma unroll
-    for (int u = 0; u < 8; ++u) acc[u] += ws[(c + u) * stride + e];
-  }
-  for (; c < S; ++c) acc[0] += ws[c * stride + e];
-  const float s = ((acc[0] + acc[1]) + (acc[2] + acc[3])) + ((acc[4] + acc[5]) + (acc[6] + acc[7]));
-  if (e < nw) dW[e] = accumulate ? dW[e] + s : s;
-  else if (db) db[e - nw] = accumulate ? db[e - nw] + s : s;
-}
-
-// the same sums for up to kReduceBatchB16 layers in one launch (descriptors by value, grid.y = layer): see
-// nsdp_wgrad_bf16_reduce_batched -- the element order and the eight chains are those of reduce_b16_kernel (bit-identical)
-constexpr int kReduceBatchB16 = 48;
-struct ReduceBatchB16 {
-  NsdpWgradB16ReduceDesc d[kReduceBatchB16];
-};
-__global__ __launch_bounds__(256) void reduce_b16_batched_kernel(ReduceBatchB16 b) {
-  const NsdpWgradB16ReduceDesc &d = b.d[blockIdx.y];
-  const long long e = blockIdx.x * 256LL + threadIdx.x;
-  const long long nw = static_cast<long long>(d.N) * d.K, nb = d.db ? d.N : 0;
-  if (e >= nw + nb) return;
-  const float *__restrict__ ws = d.ws;
-  const long long stride = nw + d.N;
-  const int S = d.S;
-  float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  int c = 0;
-  for (; c + 8 <= S; c += 8) {
-#pragma unroll
-    for (int u = 0; u < 8; ++u) acc[u] += ws[(c + u) * stride + e];
-  }
-  for (; c < S; ++c) acc[0] += ws[c * stride + e];
-  const float s = ((acc[0] + acc[1]) + (acc[2] + acc[3])) + ((acc[4] + acc[5]) + (acc[6] + acc[7]));
-  if (e < nw) d.dW[e] = d.accumulate ? d.dW[e] + s : s;
-  else d.db[e - nw] = d.accumulate ? d.db[e - nw] + s : s;
-}
-
-// out[b][e] = sum over the S partials of shape b (one-hot scatter tables)
+// (dW, db: the partials [S][N K + N] are summed by wgrad_reduce.h's linear layout, eight chains)
+// out[b][e] = sum over the S partials of shape b (one-hot scatter tables), four chains
 __global__ __launch_bounds__(256) void reduce_tables_kernel(const float *__restrict__ ws, int S, long long stride, long long nw,
                                                             float *__restrict__ out) {
   const long long e = blockIdx.x * 256LL + threadIdx.x;
   if (e >= nw) return;
-  const float *w = ws + static_cast<long long>(blockIdx.y) * S * stride + e;
-  float acc[4] = {0.f, 0.f, 0.f, 0.f};
-  int c = 0;
-  for (; c + 4 <= S; c += 4) {
-#pragma unroll
-    for (int u = 0; u < 4; ++u) acc[u] += w[(c + u) * stride];
-  }
-  for (; c < S; ++c) acc[0] += w[c * stride];
-  out[static_cast<long long>(blockIdx.y) * nw + e] = (acc[0] + acc[1]) + (acc[2] + acc[3]);
+  out[static_cast<long long>(blockIdx.y) * nw + e] = sum4(ws + static_cast<long long>(blockIdx.y) * S * stride + e, 0, S, stride);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -687,19 +629,6 @@ struct Wg16TrParams {
   int pitch_a, pitch_b;                  // bytes per image row (dY / mask, X)
   int slot_bytes, pieces;                // bytes of one ring slot (multiple of 1 KiB), DMA pieces per slab
 };
-
-template <int I, int NN, typename F>
-__device__ __forceinline__ void static_for(F &&f) {
-  if constexpr (I < NN) {
-    f(std::integral_constant<int, I>{});
-    static_for<I + 1, NN>(f);
-  }
-}
-
-template <int OFF>
-__device__ __forceinline__ void tr_read(unsigned long long &dst, unsigned addr) {
-  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF));
-}
 
 // SR: a slab (one barrier, one ring slot) is SR x 32 rows = SR MFMA steps: narrow layers move too few bytes per 32 rows
 // to pay for a barrier each
@@ -1114,26 +1043,7 @@ int nsdp_linear_wgrad_bf16_partials(const void *dY, const void *X, const void *m
 }
 
 int nsdp_wgrad_bf16_reduce_batched(const NsdpWgradB16ReduceDesc *descs, int count, void *stream) {
-  if (count <= 0) return 0;
-  NSDP_REQUIRE(descs, "wgrad_bf16_reduce_batched: null descriptor array");
-  hipStream_t st = nsdp::as_stream(stream);
-  for (int base = 0; base < count; base += kReduceBatchB16) {
-    ReduceBatchB16 b;
-    const int n = count - base < kReduceBatchB16 ? count - base : kReduceBatchB16;
-    long long blocks = 1;
-    for (int i = 0; i < n; ++i) {
-      const NsdpWgradB16ReduceDesc &e = descs[base + i];
-      NSDP_REQUIRE(e.ws && e.dW && e.S > 0 && e.N > 0 && e.K > 0, "wgrad_bf16_reduce_batched: bad descriptor %d", base + i);
-      b.d[i] = e;
-      const long long ne = static_cast<long long>(e.N) * e.K + e.N;
-      blocks = (ne + 255) / 256 > blocks ? (ne + 255) / 256 : blocks;
-    }
-    for (int i = n; i < kReduceBatchB16; ++i) b.d[i] = b.d[0];
-    hipLaunchKernelGGL(reduce_b16_batched_kernel, dim3(static_cast<unsigned>(blocks), n), dim3(256), 0, st, b);
-    const int rc = nsdp::launch_status("reduce_b16_batched_kernel");
-    if (rc) return rc;
-  }
-  return 0;
+  return reduce_batched(descs, count, "wgrad_bf16_reduce_batched", false, nsdp::as_stream(stream));
 }
 
 static int wgrad_bf16_impl(const void *dY, const void *X, const void *mask, int relu_x, float *dW, float *db, long long M, int N,
@@ -1161,14 +1071,12 @@ static int wgrad_bf16_impl(const void *dY, const void *X, const void *mask, int 
   } else if (tn <= 2 && tk <= 2) rc = launch_wg16<2, 2, 1>(p, pl.grid, st);
   else rc = launch_wg16<4, 4, 1>(p, pl.grid, st);
   if (rc) return rc;
+  const NsdpWgradB16ReduceDesc desc{workspace, dW, db, pl.grid, N, K, accumulate ? 1 : 0, 0};
   if (desc_out) {      // the caller reduces this layer's partials with a batch (nsdp_wgrad_bf16_reduce_batched)
-    *desc_out = NsdpWgradB16ReduceDesc{workspace, dW, db, pl.grid, N, K, accumulate ? 1 : 0, 0};
+    *desc_out = desc;
     return 0;
   }
-  const long long nw = static_cast<long long>(N) * K, nb = db ? N : 0;
-  hipLaunchKernelGGL(reduce_b16_kernel, dim3(static_cast<unsigned>((nw + N + 255) / 256)), dim3(256), 0, st, workspace,
-                     pl.grid, nw + N, nw, dW, static_cast<long long>(nb), db, accumulate);
-  return nsdp::launch_status("reduce_b16_kernel");
+  return reduce_one(desc, st);
 }
 
 static WgPlan plan_onehot(int B, long long rows) {

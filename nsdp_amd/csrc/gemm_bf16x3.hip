@@ -26,6 +26,7 @@
 //     and the four lane groups of a row read 64 contiguous bytes per load instruction), one
 //     k block ahead, and split on the VALU (v_cvt_pk_bf16_f32 / v_pk_add_f32: 4.5 ops per value) during
 //     the first MFMA steps of the previous k block.
+#include "wgrad_reduce.h"
 #include "x3_kernel.h"
 
 namespace nsdp {
@@ -59,15 +60,7 @@ __global__ __launch_bounds__(256) void x3_tail_reduce_kernel(const float *__rest
   const int n = e < 4 * N ? (e >> 2) : (e - 4 * N);
   const int v = e < 4 * N ? 4 * (n & 3) + (e & 3) : 16 + (n & 3);
   const long long stride = static_cast<long long>(ntiles) * 80;
-  const float *src = part + (n >> 2) * 20 + v;      // ((n / 16) * 4 + (n % 16) / 4) * 20
-  float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};      // 8 loads in flight per lane
-  int i = 0;
-  for (; i + 8 <= S; i += 8) {
-#pragma unroll
-    for (int u = 0; u < 8; ++u) acc[u] += src[(i + u) * stride];
-  }
-  for (; i < S; ++i) acc[0] += src[i * stride];
-  const float s = ((acc[0] + acc[1]) + (acc[2] + acc[3])) + ((acc[4] + acc[5]) + (acc[6] + acc[7]));
+  const float s = sum8(part + (n >> 2) * 20 + v, S, stride);      // ((n / 16) * 4 + (n % 16) / 4) * 20; eight chains
   if (e < 4 * N) {
     const int k = e & 3;
     if (k < k_out) dW[n * k_out + k] = accumulate ? dW[n * k_out + k] + s : s;
@@ -153,7 +146,7 @@ __global__ __launch_bounds__(512, 1) void linear_bf16x3_ap_kernel(X3Params p, in
       for (int c = 0; c < 4; ++c) v[c] = __builtin_amdgcn_fmed3f(v[c], 0.f, __builtin_inff());
     }
     unsigned h, m, l;
-    split_pair(v[2 * (pr & 1)], v[2 * (pr & 1) + 1], h, m, l);
+    split3(v[2 * (pr & 1)], v[2 * (pr & 1) + 1], h, m, l);
     pl.h[mt][pr] = h; pl.m[mt][pr] = m; pl.l[mt][pr] = l;
   };
   auto wrap = [&](int v) { return v >= KB ? v - KB : v; };
@@ -260,7 +253,7 @@ __global__ __launch_bounds__(512, 1) void linear_bf16x3_ap_kernel(X3Params p, in
       const unsigned wl_addr = lds0 + wb * kBufBytes;
       u32x4 wh, wm, wl;
       lds_read<0>(wh, wl_addr); lds_read<1024>(wm, wl_addr); lds_read<2048>(wl, wl_addr);
-      lds_wait(wh, wm, wl);
+      lds_wait3(wh, wm, wl);
       static_for<0, NT>([&](auto I) {
         constexpr int nt = decltype(I)::value;
         u32x4 nh, nm, nl;
@@ -308,7 +301,7 @@ __global__ __launch_bounds__(512, 1) void linear_bf16x3_ap_kernel(X3Params p, in
           }
         }
         if constexpr (nt + 1 < NT) {
-          lds_wait(nh, nm, nl);
+          lds_wait3(nh, nm, nl);
           wh = nh; wm = nm; wl = nl;
         }
       });

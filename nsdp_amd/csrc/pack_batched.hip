@@ -25,7 +25,7 @@ __global__ __launch_bounds__(256) void pack_batched_kernel(Batch b) {
     if (q < 4LL * e.N) static_cast<float *>(e.Wp)[q] = static_cast<int>(q & 3) < e.K ? e.W[(q >> 2) * e.K + (q & 3)] : 0.f;
   } else {
     if (q < nsdp::pack::x3_threads(e.N, e.K, e.Wp != nullptr, e.WpT != nullptr))
-      nsdp::pack::x3_body(e.W, e.N, e.K, static_cast<nsdp::pack::u32x4 *>(e.Wp), static_cast<nsdp::pack::u32x4 *>(e.WpT), q);
+      nsdp::pack::x3_body(e.W, e.N, e.K, static_cast<u32x4 *>(e.Wp), static_cast<u32x4 *>(e.WpT), q);
   }
 }
 

@@ -3,12 +3,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "mfma_util.h"
+
 namespace nsdp {
 namespace pack {
-
-using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
-using f32x2 = __attribute__((ext_vector_type(2))) float;
-using bf16x2 = __attribute__((ext_vector_type(2))) __bf16;
 
 // threads a launch needs (a multiple of 64)
 __host__ __device__ inline long long fp32_threads(int N, int K) {
@@ -49,16 +47,7 @@ __device__ __forceinline__ void fp32_body(const float *__restrict__ W, int N, in
   }
 }
 
-// two fp32 values -> the packed (lo, hi) bf16 pairs of their three split planes (round to nearest, exact residuals)
-__device__ __forceinline__ void split3(float x0, float x1, unsigned &h, unsigned &m, unsigned &l) {
-  h = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{x0, x1}, bf16x2));
-  const float r0 = x0 - __builtin_bit_cast(float, h << 16), r1 = x1 - __builtin_bit_cast(float, h & 0xffff0000u);
-  m = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{r0, r1}, bf16x2));
-  const float s0 = r0 - __builtin_bit_cast(float, m << 16), s1 = r1 - __builtin_bit_cast(float, m & 0xffff0000u);
-  l = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{s0, s1}, bf16x2));
-}
-
-// bf16x3 plane packs (layout: include/nsdp_hip.h, nsdp_pack_weight_bf16x3; kperm(g, j) = 16 (j / 4) + 4 g + j % 4)
+// bf16x3 plane packs (split3: mfma_util.h) (layout: include/nsdp_hip.h, nsdp_pack_weight_bf16x3; kperm(g, j) = 16 (j / 4) + 4 g + j % 4)
 __device__ __forceinline__ void x3_body(const float *__restrict__ W, int N, int K, u32x4 *__restrict__ Wp,
                                         u32x4 *__restrict__ WpT, long long q) {
   const int lane = static_cast<int>(q & 63), li = lane & 15, g = lane >> 4;

@@ -25,15 +25,11 @@
 
 #include "common.h"
 #include "k4.h"
+#include "mfma_util.h"
 #include "prof.h"
+#include "wgrad_reduce.h"
 
 namespace {
-
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-using f32x2 = __attribute__((ext_vector_type(2))) float;
-using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
-using bf16x2 = __attribute__((ext_vector_type(2))) __bf16;
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
 
 typedef __attribute__((address_space(3))) void *lds_ptr_t;
 
@@ -63,26 +59,6 @@ struct WgX3Params {
   const unsigned char *bits = nullptr;
 };
 
-__device__ __forceinline__ void split_pair(float x0, float x1, unsigned &h, unsigned &m, unsigned &l) {
-  h = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{x0, x1}, bf16x2));
-  const float r0 = x0 - __builtin_bit_cast(float, h << 16), r1 = x1 - __builtin_bit_cast(float, h & 0xffff0000u);
-  m = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{r0, r1}, bf16x2));
-  const float s0 = r0 - __builtin_bit_cast(float, m << 16), s1 = r1 - __builtin_bit_cast(float, m & 0xffff0000u);
-  l = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{s0, s1}, bf16x2));
-}
-
-__device__ __forceinline__ f32x4 mfma_bf16(u32x4 a, u32x4 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-
-template <int I, int N, typename F>
-__device__ __forceinline__ void static_for(F &&f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>{});
-    static_for<I + 1, N>(f);
-  }
-}
-
 __device__ __forceinline__ const float *sgpr_ptr(const float *q) {   // pin a wave-uniform pointer into SGPRs
   const unsigned long long u = reinterpret_cast<unsigned long long>(q);
   const unsigned lo = __builtin_amdgcn_readfirstlane(static_cast<unsigned>(u));
@@ -93,13 +69,6 @@ __device__ __forceinline__ const float *sgpr_ptr(const float *q) {   // pin a wa
 // hand-placed memory operations (the compiler sinks ordinary loads to their first use; see decoder_fused.hip)
 __device__ __forceinline__ void gload(float &dst, const float *uniform_base, unsigned byte_off) {
   asm volatile("global_load_dword %0, %1, %2" : "=v"(dst) : "v"(byte_off), "s"(uniform_base));
-}
-template <int OFF>
-__device__ __forceinline__ void lds_read(u32x4 &dst, unsigned addr) {
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF));
-}
-__device__ __forceinline__ void lds_wait3(u32x4 &a, u32x4 &b, u32x4 &c) {
-  asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a), "+v"(b), "+v"(c));
 }
 
 // NTA / KTB: 16-column tiles of dY / X.  Wave (a, b) = (wave >> 1, wave & 1) owns n tiles [a TA, a TA + TA) and
@@ -124,11 +93,7 @@ __device__ __forceinline__ void gload4(f32x4 &dst, const float *uniform_base, un
 __device__ __forceinline__ void gload_i32(int &dst, const float *uniform_base, unsigned byte_off) {
   asm volatile("global_load_dword %0, %1, %2" : "=v"(dst) : "v"(byte_off), "s"(uniform_base));
 }
-template <int OFF>
-__device__ __forceinline__ void tr_read(unsigned long long &dst, unsigned addr) {
-  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF));
-}
-struct Frag3 {
+struct Frag3 {      // the two halves (mfma_util.h: tr_read) of an operand's three planes
   unsigned long long h[2], m[2], l[2];
 };
 __device__ __forceinline__ void frag_wait_h(Frag3 &f) {      // (one-hot operand: only the h plane exists)
@@ -323,8 +288,8 @@ __global__ __launch_bounds__(256) void wgrad_bf16x3_rows_kernel(WgX3Params p) {
   };
   auto write3 = [&](const f32x4 &v, unsigned byte_off, int plane_bytes) {
     unsigned h0, m0, l0, h1, m1, l1;
-    split_pair(v[0], v[1], h0, m0, l0);
-    split_pair(v[2], v[3], h1, m1, l1);
+    split3(v[0], v[1], h0, m0, l0);
+    split3(v[2], v[3], h1, m1, l1);
     unsigned char *dst = &planes[0] + byte_off;
     *reinterpret_cast<unsigned long long *>(dst) = (static_cast<unsigned long long>(h1) << 32) | h0;
     *reinterpret_cast<unsigned long long *>(dst + plane_bytes) = (static_cast<unsigned long long>(m1) << 32) | m0;
@@ -549,103 +514,8 @@ __global__ __launch_bounds__(256) void wgrad_bf16x3_rows_kernel(WgX3Params p) {
   }
 }
 
-// dW[n][k] = sum over the S partials of element (n, k): accumulator (tile n/16, tile k/16), lane 16 (n%16)/4 + k%16,
-// register (n%16)%4  (C/D layout of the MFMA: row = 4 (lane >> 4) + reg, column = lane & 15).
-// 32 elements x 8 partial ranges per workgroup: a thread sums one eighth of the partials of one element (S/8
-// independent loads in flight instead of a chain of S), the eight sub-sums are combined through LDS in fixed order.
-__global__ __launch_bounds__(256) void wgrad_bf16x3_reduce_kernel(const float *__restrict__ ws, int S, int NTA, int KTB,
-                                                                  int N, int K, float *__restrict__ dW,
-                                                                  float *__restrict__ db, int accumulate) {
-  __shared__ float part[8][32];
-  const int el = threadIdx.x & 31, q = threadIdx.x >> 5;
-  const long long e = static_cast<long long>(blockIdx.x) * 32 + el;
-  const long long nw = static_cast<long long>(N) * K;
-  const size_t stride = static_cast<size_t>(NTA) * KTB * 256 + NTA * 16;
-  size_t idx = 0;
-  bool valid = true;
-  if (e < nw) {
-    const int n = static_cast<int>(e / K), kg = static_cast<int>(e % K);
-    const int part = kg / (KTB * 16), k = kg - part * KTB * 16;       // column range (grid.y of the main kernel)
-    const int nl = n & 15, kl = k & 15;
-    idx = static_cast<size_t>(part) * S * stride +
-          (static_cast<size_t>(n >> 4) * KTB + (k >> 4)) * 256 + (16 * (nl >> 2) + kl) * 4 + (nl & 3);
-  } else if (e < nw + N && db) {
-    idx = static_cast<size_t>(NTA) * KTB * 256 + (e - nw);
-  } else {
-    valid = false;
-  }
-  float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-  if (valid) {
-    const int per = (S + 7) / 8;
-    int s = q * per;
-    const int s_end = s + per < S ? s + per : S;
-    for (; s + 4 <= s_end; s += 4) {
-      s0 += ws[idx + (s + 0) * stride]; s1 += ws[idx + (s + 1) * stride];
-      s2 += ws[idx + (s + 2) * stride]; s3 += ws[idx + (s + 3) * stride];
-    }
-    for (; s < s_end; ++s) s0 += ws[idx + s * stride];
-  }
-  part[q][el] = (s0 + s1) + (s2 + s3);
-  __syncthreads();
-  if (q == 0 && valid) {
-    const float t = ((part[0][el] + part[1][el]) + (part[2][el] + part[3][el])) +
-                    ((part[4][el] + part[5][el]) + (part[6][el] + part[7][el]));
-    if (e < nw) dW[e] = accumulate ? dW[e] + t : t;
-    else db[e - nw] = accumulate ? db[e - nw] + t : t;
-  }
-}
-
-// The same sums for up to kReduceBatch layers in ONE launch (descriptors by value in the kernel arguments, grid.y = layer,
-// grid.x covers the largest layer): element order, partial ranges and the combination are those of the kernel above, so a
-// gradient does not depend on which of the two reduced it.
-constexpr int kReduceBatch = 48;
-struct ReduceBatch {
-  NsdpWgradReduceDesc d[kReduceBatch];
-};
-__global__ __launch_bounds__(256) void wgrad_bf16x3_reduce_batched_kernel(ReduceBatch b) {
-  __shared__ float part[8][32];
-  const NsdpWgradReduceDesc &e = b.d[blockIdx.y];
-  const int N = e.N, K = e.K, S = e.S, NTA = e.nta, KTB = e.ktb;
-  const long long nw = static_cast<long long>(N) * K;
-  const long long ne = nw + (e.db ? N : 0);
-  if (static_cast<long long>(blockIdx.x) * 32 >= ne) return;      // (uniform per workgroup)
-  const float *__restrict__ ws = e.ws;
-  const int el = threadIdx.x & 31, q = threadIdx.x >> 5;
-  const long long el_g = static_cast<long long>(blockIdx.x) * 32 + el;
-  const size_t stride = static_cast<size_t>(NTA) * KTB * 256 + NTA * 16;
-  size_t idx = 0;
-  bool valid = true;
-  if (el_g < nw) {
-    const int n = static_cast<int>(el_g / K), kg = static_cast<int>(el_g % K);
-    const int kpart = kg / (KTB * 16), k = kg - kpart * KTB * 16;
-    const int nl = n & 15, kl = k & 15;
-    idx = static_cast<size_t>(kpart) * S * stride +
-          (static_cast<size_t>(n >> 4) * KTB + (k >> 4)) * 256 + (16 * (nl >> 2) + kl) * 4 + (nl & 3);
-  } else if (el_g < nw + N && e.db) {
-    idx = static_cast<size_t>(NTA) * KTB * 256 + (el_g - nw);
-  } else {
-    valid = false;
-  }
-  float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-  if (valid) {
-    const int per = (S + 7) / 8;
-    int s = q * per;
-    const int s_end = s + per < S ? s + per : S;
-    for (; s + 4 <= s_end; s += 4) {
-      s0 += ws[idx + (s + 0) * stride]; s1 += ws[idx + (s + 1) * stride];
-      s2 += ws[idx + (s + 2) * stride]; s3 += ws[idx + (s + 3) * stride];
-    }
-    for (; s < s_end; ++s) s0 += ws[idx + s * stride];
-  }
-  part[q][el] = (s0 + s1) + (s2 + s3);
-  __syncthreads();
-  if (q == 0 && valid) {
-    const float t = ((part[0][el] + part[1][el]) + (part[2][el] + part[3][el])) +
-                    ((part[4][el] + part[5][el]) + (part[6][el] + part[7][el]));
-    if (el_g < nw) e.dW[el_g] = e.accumulate ? e.dW[el_g] + t : t;
-    else e.db[el_g - nw] = e.accumulate ? e.db[el_g - nw] + t : t;
-  }
-}
+// (dW, db: the partials are summed by wgrad_reduce.h's fragment layout -- eight ranges of four chains -- behind a one-call entry
+// or, through the descriptor a partials form hands out, by nsdp_wgrad_bf16x3_reduce_batched)
 
 thread_local int g_wg3_reserve = 0;      // host hint 9: per host thread (autograd runs one backward thread per device)
 
@@ -718,23 +588,48 @@ bool launch_wg_g16(const WgX3Params &p, int layout, int grid, hipStream_t st) {
   return true;
 }
 
-// table[b][n][k] = sum over the S partials of shape b (fragment order, see wgrad_bf16x3_reduce_kernel), fixed order
+// The launch tail of the four weight-gradient entries.  The row kernel of the plan's tile class -- layout 0: row-major operands
+// (launch_wg; the H0 form where p.h_w0 is set), 1 / 2: G16 operands (their square classes only) -- then the reduction of its
+// partials as a descriptor: handed out for nsdp_wgrad_bf16x3_reduce_batched (desc_out != NULL), or reduced here.
+int launch_rows_then_reduce(const WgX3Params &p, const X3Plan &pl, int layout, const char *rows_kernel, float *dW, float *db,
+                            int accumulate, NsdpWgradReduceDesc *desc_out, hipStream_t st) {
+  auto rows = [&](auto A, auto B) {
+    constexpr int NTA = decltype(A)::value, KTB = decltype(B)::value;
+    if (layout == 0) {
+      launch_wg<NTA, KTB>(p, pl.grid, st);
+      return true;
+    }
+    if constexpr ((NTA == 8 && KTB == 8) || (NTA == 13 && KTB == 13) || (NTA == 16 && KTB == 8))
+      return launch_wg_g16<NTA, KTB>(p, layout, pl.grid, st);
+    return false;
+  };
+  const std::integral_constant<int, 8> c8;
+  const std::integral_constant<int, 13> c13;
+  const std::integral_constant<int, 16> c16;
+  const bool ok = pl.nta == 8 && pl.ktb == 8 ? rows(c8, c8)
+                  : pl.nta == 8              ? rows(c8, c13)
+                  : pl.nta == 16             ? rows(c16, c8)
+                  : pl.ktb == 8              ? rows(c13, c8)
+                                             : rows(c13, c13);
+  NSDP_REQUIRE(ok, "linear_wgrad_bf16x3_g16: form not instantiated");      // (layout 0 has every class)
+  const int rc = nsdp::launch_status(rows_kernel);
+  if (rc) return rc;
+  const NsdpWgradReduceDesc desc{p.ws, dW, db, pl.grid, pl.nta, pl.ktb, p.N, p.K, accumulate ? 1 : 0, 0};
+  if (desc_out) {
+    *desc_out = desc;
+    return 0;
+  }
+  return reduce_one(desc, st);
+}
+
+// table[b][n][k] = sum over the S partials of shape b (fragment layout of wgrad_reduce.h, one column part: K <= 16 KTB), four chains
 __global__ __launch_bounds__(256) void onehot_tables_reduce_kernel(const float *__restrict__ ws, int S, int NTA, int KTB, int N,
                                                                    int K, float *__restrict__ table) {
   const long long e = static_cast<long long>(blockIdx.x) * 256 + threadIdx.x;
   if (e >= static_cast<long long>(N) * K) return;
-  const int n = static_cast<int>(e / K), k = static_cast<int>(e % K);
-  const int nl = n & 15, kl = k & 15;
-  const size_t stride = static_cast<size_t>(NTA) * KTB * 256 + NTA * 16;
-  const float *w = ws + static_cast<size_t>(blockIdx.y) * S * stride +
-                   (static_cast<size_t>(n >> 4) * KTB + (k >> 4)) * 256 + (16 * (nl >> 2) + kl) * 4 + (nl & 3);
-  float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-  int s = 0;
-  for (; s + 4 <= S; s += 4) {
-    a0 += w[(s + 0) * stride]; a1 += w[(s + 1) * stride]; a2 += w[(s + 2) * stride]; a3 += w[(s + 3) * stride];
-  }
-  for (; s < S; ++s) a0 += w[s * stride];
-  table[static_cast<long long>(blockIdx.y) * N * K + e] = (a0 + a1) + (a2 + a3);
+  const long long stride = fragment_stride(NTA, KTB);
+  const float *w = ws + blockIdx.y * S * stride + fragment_offset(S, NTA, KTB, static_cast<int>(e / K), static_cast<int>(e % K));
+  table[static_cast<long long>(blockIdx.y) * N * K + e] = sum4(w, 0, S, stride);
 }
 
 struct OneHotPlan {
@@ -785,13 +680,7 @@ int nsdp_linear_wgrad_bf16x3_partials_f32(const float *dY, const float *X, const
   WgX3Params p{dY, X, mask, relu_x, workspace, M, N, K, pl.blocks_per_wg, db != nullptr, pl.kparts};
   hipStream_t st = nsdp::as_stream(stream);
   nsdp::prof::Scope scope(nsdp::prof::kWgradX3, st, 2.0 * M * N * K, 4.0 * (static_cast<double>(M) * (K + N)));
-  if (pl.nta == 8 && pl.ktb == 8) launch_wg<8, 8>(p, pl.grid, st);
-  else if (pl.nta == 8) launch_wg<8, 13>(p, pl.grid, st);
-  else if (pl.nta == 16) launch_wg<16, 8>(p, pl.grid, st);
-  else if (pl.ktb == 8) launch_wg<13, 8>(p, pl.grid, st);
-  else launch_wg<13, 13>(p, pl.grid, st);
-  *desc_out = NsdpWgradReduceDesc{workspace, dW, db, pl.grid, pl.nta, pl.ktb, N, K, accumulate ? 1 : 0, 0};
-  return nsdp::launch_status("wgrad_bf16x3_kernel");
+  return launch_rows_then_reduce(p, pl, 0, "wgrad_bf16x3_kernel", dW, db, accumulate, desc_out, st);
 }
 
 // dW [N,K], db [N] of the SECOND layer of a position-encoding MLP Linear(3 or 4, K) -> ReLU -> Linear(K, N) from the gradient
@@ -819,44 +708,11 @@ int nsdp_linear_wgrad_bf16x3_h0_f32(const float *dY, const float *X4, const floa
   p.h_w0 = W0; p.h_b0 = b0;
   hipStream_t st = nsdp::as_stream(stream);
   nsdp::prof::Scope scope(nsdp::prof::kWgradX3, st, 2.0 * M * N * K, 4.0 * (static_cast<double>(M) * (4 + N)));
-  if (pl.nta == 8) launch_wg<8, 8>(p, pl.grid, st);
-  else if (pl.nta == 16) launch_wg<16, 8>(p, pl.grid, st);
-  else launch_wg<13, 13>(p, pl.grid, st);
-  const int rc = nsdp::launch_status("wgrad_bf16x3_kernel (h0)");
-  if (rc) return rc;
-  if (desc_out) {
-    *desc_out = NsdpWgradReduceDesc{workspace, dW, db, pl.grid, pl.nta, pl.ktb, N, K, accumulate ? 1 : 0, 0};
-    return 0;
-  }
-  const long long ne = static_cast<long long>(N) * K + N;
-  hipLaunchKernelGGL(wgrad_bf16x3_reduce_kernel, dim3(static_cast<unsigned>((ne + 31) / 32)), dim3(256), 0, st,
-                     workspace, pl.grid, pl.nta, pl.ktb, N, K, dW, db, accumulate);
-  return nsdp::launch_status("wgrad_bf16x3_reduce_kernel");
+  return launch_rows_then_reduce(p, pl, 0, "wgrad_bf16x3_kernel (h0)", dW, db, accumulate, desc_out, st);
 }
 
 int nsdp_wgrad_bf16x3_reduce_batched(const NsdpWgradReduceDesc *descs, int count, void *stream) {
-  if (count <= 0) return 0;
-  NSDP_REQUIRE(descs, "wgrad_bf16x3_reduce_batched: null descriptor array");
-  hipStream_t st = nsdp::as_stream(stream);
-  for (int base = 0; base < count; base += kReduceBatch) {
-    ReduceBatch b;
-    const int n = count - base < kReduceBatch ? count - base : kReduceBatch;
-    long long blocks = 1;
-    for (int i = 0; i < n; ++i) {
-      const NsdpWgradReduceDesc &e = descs[base + i];
-      NSDP_REQUIRE(e.ws && e.dW && e.S > 0 && e.N > 0 && e.K > 0 && e.nta > 0 && e.ktb > 0,
-                   "wgrad_bf16x3_reduce_batched: bad descriptor %d", base + i);
-      b.d[i] = e;
-      const long long ne = static_cast<long long>(e.N) * e.K + (e.db ? e.N : 0);
-      blocks = (ne + 31) / 32 > blocks ? (ne + 31) / 32 : blocks;
-    }
-    for (int i = n; i < kReduceBatch; ++i) b.d[i] = b.d[0];      // never indexed (grid.y = n)
-    NSDP_TRACE("wgrad_bf16x3_reduce_batched x%d", n);
-    hipLaunchKernelGGL(wgrad_bf16x3_reduce_batched_kernel, dim3(static_cast<unsigned>(blocks), n), dim3(256), 0, st, b);
-    const int rc = nsdp::launch_status("wgrad_bf16x3_reduce_batched_kernel");
-    if (rc) return rc;
-  }
-  return 0;
+  return reduce_batched(descs, count, "wgrad_bf16x3_reduce_batched", true, nsdp::as_stream(stream));
 }
 
 int nsdp_linear_wgrad_bf16x3_f32(const float *dY, const float *X, const float *mask, int relu_x, float *dW,
@@ -871,23 +727,11 @@ int nsdp_linear_wgrad_bf16x3_f32(const float *dY, const float *X, const float *m
   WgX3Params p{dY, X, mask, relu_x, workspace, M, N, K, pl.blocks_per_wg, db != nullptr, pl.kparts};
   hipStream_t st = nsdp::as_stream(stream);
   nsdp::prof::Scope scope(nsdp::prof::kWgradX3, st, 2.0 * M * N * K, 4.0 * (static_cast<double>(M) * (K + N)));
-  {
-    if (pl.nta == 8 && pl.ktb == 8) launch_wg<8, 8>(p, pl.grid, st);
-    else if (pl.nta == 8) launch_wg<8, 13>(p, pl.grid, st);
-    else if (pl.nta == 16) launch_wg<16, 8>(p, pl.grid, st);
-    else if (pl.ktb == 8) launch_wg<13, 8>(p, pl.grid, st);
-    else launch_wg<13, 13>(p, pl.grid, st);
-    const int rc = nsdp::launch_status("wgrad_bf16x3_kernel");
-    if (rc) return rc;
-  }
-  const long long ne = static_cast<long long>(N) * K + N;
   // (ablation, timing only, wrong results: NSDP_WG3_SKIP_REDUCE=1 drops the reduce launch -- the ceiling of what folding or
-  // batching the 98 reduce launches of a step could buy)
+  // batching the 98 reduce launches of a step could buy: the reduction is described to nobody)
   static const bool skip_reduce = getenv("NSDP_WG3_SKIP_REDUCE") && atoi(getenv("NSDP_WG3_SKIP_REDUCE")) != 0;
-  if (skip_reduce) return 0;
-  hipLaunchKernelGGL(wgrad_bf16x3_reduce_kernel, dim3(static_cast<unsigned>((ne + 31) / 32)), dim3(256), 0, st,
-                     workspace, pl.grid, pl.nta, pl.ktb, N, K, dW, db, accumulate);
-  return nsdp::launch_status("wgrad_bf16x3_reduce_kernel");
+  NsdpWgradReduceDesc dropped;
+  return launch_rows_then_reduce(p, pl, 0, "wgrad_bf16x3_kernel", dW, db, accumulate, skip_reduce ? &dropped : nullptr, st);
 }
 
 // nsdp_linear_wgrad_bf16x3_f32 / _partials_f32 with operands in the G16 layout (gemm_bf16x3_g16.hip): layout bit 0 = dY and the
@@ -912,19 +756,7 @@ int nsdp_linear_wgrad_bf16x3_g16_f32(const float *dY, const float *X, const floa
   p.bits = mask_bits;
   hipStream_t st = nsdp::as_stream(stream);
   nsdp::prof::Scope scope(nsdp::prof::kWgradX3, st, 2.0 * M * N * K, 4.0 * (static_cast<double>(M) * (K + N)));
-  const bool ok = pl.nta == 8 ? launch_wg_g16<8, 8>(p, layout, pl.grid, st)
-                  : pl.nta == 16 ? launch_wg_g16<16, 8>(p, layout, pl.grid, st) : launch_wg_g16<13, 13>(p, layout, pl.grid, st);
-  NSDP_REQUIRE(ok, "linear_wgrad_bf16x3_g16: form not instantiated");
-  const int rc = nsdp::launch_status("wgrad_bf16x3_kernel (g16)");
-  if (rc) return rc;
-  if (desc_out) {
-    *desc_out = NsdpWgradReduceDesc{workspace, dW, db, pl.grid, pl.nta, pl.ktb, N, K, accumulate ? 1 : 0, 0};
-    return 0;
-  }
-  const long long ne = static_cast<long long>(N) * K + N;
-  hipLaunchKernelGGL(wgrad_bf16x3_reduce_kernel, dim3(static_cast<unsigned>((ne + 31) / 32)), dim3(256), 0, st,
-                     workspace, pl.grid, pl.nta, pl.ktb, N, K, dW, db, accumulate);
-  return nsdp::launch_status("wgrad_bf16x3_reduce_kernel");
+  return launch_rows_then_reduce(p, pl, layout, "wgrad_bf16x3_kernel (g16)", dW, db, accumulate, desc_out, st);
 }
 
 size_t nsdp_scatter_rows_onehot_f32_workspace_bytes(int B, long long rows, int N, int d) {

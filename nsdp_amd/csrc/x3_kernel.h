@@ -8,6 +8,7 @@
 
 #include "common.h"
 #include "k4.h"
+#include "mfma_util.h"
 #include "pack_bodies.h"
 #include "prof.h"
 
@@ -17,12 +18,6 @@ extern thread_local int g_x3_side_reserve;   // (per host thread) compute units 
 }  // namespace nsdp
 
 namespace {
-
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-using f32x2 = __attribute__((ext_vector_type(2))) float;
-using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
-using bf16x2 = __attribute__((ext_vector_type(2))) __bf16;
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
 
 typedef __attribute__((address_space(3))) void *lds_ptr_t;
 typedef const __attribute__((address_space(1))) void *gbl_ptr_t;
@@ -93,27 +88,6 @@ constexpr int kLayX = 1;      // X (and the PRE == 1 mask)
 constexpr int kLayY = 2;      // Y: stored straight from the accumulators, one contiguous KiB per tile, no LDS staging
 constexpr int kLayR = 4;      // the residual (it only initialises the accumulators: independent of Y's layout)
 
-// two fp32 values -> the packed (lo, hi) bf16 pairs of their three split planes
-__device__ __forceinline__ void split_pair(float x0, float x1, unsigned &h, unsigned &m, unsigned &l) {
-  h = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{x0, x1}, bf16x2));
-  const float r0 = x0 - __builtin_bit_cast(float, h << 16), r1 = x1 - __builtin_bit_cast(float, h & 0xffff0000u);
-  m = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{r0, r1}, bf16x2));
-  const float s0 = r0 - __builtin_bit_cast(float, m << 16), s1 = r1 - __builtin_bit_cast(float, m & 0xffff0000u);
-  l = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{s0, s1}, bf16x2));
-}
-
-__device__ __forceinline__ f32x4 mfma_bf16(u32x4 a, u32x4 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-
-template <int I, int N, typename F>
-__device__ __forceinline__ void static_for(F &&f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>{});
-    static_for<I + 1, N>(f);
-  }
-}
-
 // Sums over the 16 lanes of a DPP row (lanes 16 r .. 16 r + 15) of 20 values at once, the totals in every lane; fixed order:
 // pairs, quads, halves, row.  One v_add_f32 with a DPP operand per value and step -- left to the compiler this became
 // v_mov 0 / v_mov_dpp / v_pk_add (2.5 instructions per step).  Written as four blocks of 20 independent instructions: the
@@ -168,18 +142,7 @@ __device__ __forceinline__ void bload(unsigned &dst, const unsigned char *lane_p
   asm volatile("global_load_ubyte %0, %1, off" : "=v"(dst) : "v"(lane_ptr));
 }
 
-
-// weight fragments come back from LDS through hand-placed ds_read_b128 (the compiler sinks ordinary LDS loads
-// below the MFMA block of a step, exposing their latency every step); lgkmcnt is awaited by hand, the fragment
-// registers being in/out operands of the wait so that their users depend on it
-template <int OFF>
-__device__ __forceinline__ void lds_read(u32x4 &dst, unsigned lane_addr) {
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(lane_addr), "n"(OFF));
-}
-__device__ __forceinline__ void lds_wait(u32x4 &a, u32x4 &b, u32x4 &c) {
-  asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a), "+v"(b), "+v"(c));
-}
-
+// (the weight fragments come back from LDS through mfma_util.h's hand-placed lds_read / lds_wait3)
 // helpers of the staged epilogue (immediate offsets, counted waits; see linear_bf16x3_kernel)
 typedef __attribute__((address_space(3))) f32x4 *lds_f4_ptr;
 // (the epilogue's LDS traffic is plain C++: under register pressure the compiler parks the destination of a hand-issued
@@ -392,7 +355,7 @@ __global__ __launch_bounds__(WV * 64, XREG ? 2 : 1) void linear_bf16x3_kernel(X3
       const float4 xq = make_float4(h_xs[mt][0], h_xs[mt][1], h_xs[mt][2], h_xs[mt][3]);
       const f32x2 pre = nsdp::k4_preact_pair(xq, f32x2{wa[0], wa[1]}, f32x2{wa[2], wa[3]}, f32x2{wb[0], wb[1]}, f32x2{wb[2], wb[3]}, bb);
       unsigned h, m, l;
-      split_pair(fmaxf(pre[0], 0.f), fmaxf(pre[1], 0.f), h, m, l);
+      split3(fmaxf(pre[0], 0.f), fmaxf(pre[1], 0.f), h, m, l);
       pl.h[mt][pr] = h; pl.m[mt][pr] = m; pl.l[mt][pr] = l;
       return;
     }
@@ -417,7 +380,7 @@ __global__ __launch_bounds__(WV * 64, XREG ? 2 : 1) void linear_bf16x3_kernel(X3
       for (int c = 0; c < 4; ++c) v[c] = __builtin_amdgcn_fmed3f(v[c], 0.f, __builtin_inff());   // max(v, 0), one VALU op
     }
     unsigned h, m, l;
-    split_pair(v[2 * (pr & 1)], v[2 * (pr & 1) + 1], h, m, l);
+    split3(v[2 * (pr & 1)], v[2 * (pr & 1) + 1], h, m, l);
     pl.h[mt][pr] = h; pl.m[mt][pr] = m; pl.l[mt][pr] = l;
   };
 
@@ -564,7 +527,7 @@ __global__ __launch_bounds__(WV * 64, XREG ? 2 : 1) void linear_bf16x3_kernel(X3
       const unsigned wl_addr = lds0 + wsel * kBufBytes + (wsel >= 1u ? kExtBytes : 0u);
       u32x4 wh, wm, wl;
       lds_read<0>(wh, wl_addr); lds_read<1024>(wm, wl_addr); lds_read<2048>(wl, wl_addr);
-      lds_wait(wh, wm, wl);
+      lds_wait3(wh, wm, wl);
       static_for<0, NT>([&](auto I) {
         constexpr int nt = decltype(I)::value;
         u32x4 nh, nm, nl;
@@ -629,7 +592,7 @@ __global__ __launch_bounds__(WV * 64, XREG ? 2 : 1) void linear_bf16x3_kernel(X3
           }
         }
         if constexpr (nt + 1 < NT) {
-          lds_wait(nh, nm, nl);
+          lds_wait3(nh, nm, nl);
           wh = nh; wm = nm; wl = nl;
         }
       });
