@@ -281,7 +281,8 @@ __global__ __launch_bounds__(kBig) void scatter_cm_lists_sliced_kernel(const flo
       cur[t] = s < N ? off[s] : 0;
       end[t] = s < N ? off[s + 1] : 0;
       // a list longer than nsdp_knn_invert sorts (a hot source point) is in arbitrary order: every slice walks the whole
-      // list and takes what falls into it (correct; slow; its summation order is the list's)
+      // list and takes what falls into it (correct; slow; summed slice after slice, in the list's order inside a slice: the
+      // list's own order only where it is ascending, as nsdp_knn_invert_wide writes it)
       unsorted[t] = end[t] - cur[t] > kListSortMax;
       nxt[t] = (cur[t] < end[t] && !unsorted[t]) ? ent[cur[t]] : kDone;
 #pragma unroll

@@ -180,6 +180,7 @@ int nsdp_knn_invert(const int32_t *idx, int B, int E, int N, int32_t *offsets, i
   if (lds > 60 * 1024) {      // (per call: the attribute belongs to the current device's function object)
     NSDP_HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
   }
+  NSDP_TRACE("knn_invert<%s>", in_lds ? "lds" : "global");
   if (in_lds) hipLaunchKernelGGL(knn_invert_kernel<true>, dim3(B), dim3(kInvThreads), lds, st, idx, E, N, offsets, entries);
   else hipLaunchKernelGGL(knn_invert_kernel<false>, dim3(B), dim3(kInvThreads), lds, st, idx, E, N, offsets, entries);
   return nsdp::launch_status("knn_invert_kernel");

@@ -133,6 +133,9 @@ def test_inverse_lists_and_segment_sum(B, n, N, k, d):
     idx[:, :, 0] = 5                                     # one hot source, many empty ones
     off, ent = ha.inverse_lists(idx, N)
     off_c, ent_c, flat = off.cpu(), ent.cpu(), idx.reshape(B, -1).cpu()
+    from list_sum_ref import inverse_lists_ref
+    want_off, want_ent = inverse_lists_ref(flat.numpy(), N)      # every list, whole: the stable sort of e by idx[b][e]
+    assert torch.equal(off_c, torch.from_numpy(want_off)) and torch.equal(ent_c, torch.from_numpy(want_ent))
     for b in range(B):
         assert off_c[b, 0] == 0 and off_c[b, N] == n * k
         assert torch.equal(torch.sort(ent_c[b]).values, torch.arange(n * k, dtype=torch.int32))     # a permutation
