@@ -23,9 +23,14 @@ def optimizer_factory(config, parameters):
     parameters = list(parameters)
     group = {"params": parameters, "lr": schedule.get_learning_rate(0),
              "weight_decay": config.get("weight_decay", 0.0)}
+    # clip_grad_norm / skip_nonfinite_steps (extensions, nsdp_amd/grad_clip.py): either key puts the global-norm clip and the
+    # skip rule at the head of the optimizer's step(); with both absent the classes below are what they always were
+    from ..grad_clip import ClippedAdam, ClippedSGD, settings
+    max_norm, skip = settings(config)
+    clip = {"max_grad_norm": max_norm, "skip_nonfinite": skip} if (max_norm is not None or skip) else None
     if name == "SGD":
         group["momentum"] = config.get("momentum", 0.9)
-        return schedule, torch.optim.SGD([group])
+        return schedule, (torch.optim.SGD([group]) if clip is None else ClippedSGD([group], **clip))
     if name == "Adam":
         # GPU parameters: the whole update as one launch of csrc/adam.hip behind torch.optim.Adam's own container
         # (hip_adam.HipAdam; NSDP_HIP_ADAM=0 keeps PyTorch's kernels for an A/B).  CPU parameters (host-side tests, the
@@ -33,8 +38,8 @@ def optimizer_factory(config, parameters):
         if (parameters and all(p.is_cuda and p.dtype == torch.float32 for p in parameters)
                 and os.environ.get("NSDP_HIP_ADAM", "1") != "0"):
             from ..hip_adam import HipAdam
-            return schedule, HipAdam([group])
-        return schedule, torch.optim.Adam([group])
+            return schedule, (HipAdam([group]) if clip is None else HipAdam([group], **clip))
+        return schedule, (torch.optim.Adam([group]) if clip is None else ClippedAdam([group], **clip))
     raise NotImplementedError(name)
 
 

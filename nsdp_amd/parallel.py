@@ -261,6 +261,9 @@ class DataParallel:
       takes the same number of steps (the gradient exchange is a collective);
     * one exchange per step: the mean of the flat fp32 gradient (GradAllReducer), then the identical Adam update on every
       rank -- weights stay bit-equal across ranks (``in_sync``);
+    * ``training.clip_grad_norm`` / ``skip_nonfinite_steps`` (nsdp_amd/grad_clip.py) act inside ``optimizer.step()``, i.e. BEHIND
+      the exchange: every rank computes the same sum of squares from the same averaged gradient (a fixed-order sum, a function of
+      the values alone), so the clip factor and the decision to skip a step are identical on all ranks with no extra collective;
     * BatchNorm: batch statistics are per rank (the reference has no SyncBN).  The running buffers are therefore per rank
       too; rank 0's are THE model's (as with torch DDP's ``broadcast_buffers``): they are broadcast to every rank before a
       validation pass and before a checkpoint, so every rank evaluates -- and rank 0 saves -- the same model;

@@ -90,6 +90,13 @@ def fit(model, fns, lr_scheduler, optimizer, train_loader, val_loader, config, e
         epoch_loss = avg.value if dp is None else dp.mean(avg.value, device)
         if main:
             log("epoch: {} - batches: {} - loss: {:.5f}".format(i + 1, avg.count, epoch_loss))
+        # (training.clip_grad_norm / skip_nonfinite_steps: ONE read of the optimizer's statistics per epoch, never per step;
+        # under dp every rank holds the same numbers -- the same averaged gradient, the same fixed-order sum.  None: an
+        # optimizer that could clip but was built without the keys)
+        st = optimizer.grad_stats() if main and hasattr(optimizer, "grad_stats") else None
+        if st is not None:
+            log("epoch: {} - gradient norm (last step): {:.5g} - clipped {} / {} steps - skipped {}".format(
+                i + 1, st["norm"], st["clipped"], st["steps"], st["skipped"]))
         history.append(("train", i, epoch_loss))
         want_val = i % val_every == 0 and i > 0
         if dp is not None and ((i % save_every) == 0 or want_val):
@@ -225,6 +232,12 @@ def main(argv=None):
                          "ranks, one RCCL all-reduce of the flat gradient per step, rank-0 checkpoints).  From a bare shell "
                          "the ranks are launched here; under torchrun (RANK / WORLD_SIZE set) this process is one of them")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend of the data-parallel job (nccl = RCCL)")
+    ap.add_argument("--clip-grad-norm", dest="clip_grad_norm", type=float, default=None, metavar="X",
+                    help="overrides training.clip_grad_norm: a bound X > 0 on the L2 norm of all gradients together, applied "
+                         "inside the optimizer step (after the data-parallel exchange); the gradients themselves are not rewritten")
+    ap.add_argument("--skip-nonfinite", dest="skip_nonfinite", action="store_true",
+                    help="sets training.skip_nonfinite_steps: a step whose gradient holds an inf or a NaN changes no weight and no "
+                         "optimizer state, and is counted in the per-epoch gradient line")
     args = ap.parse_args(argv)
     if args.dataset and args.synthetic is not None:
         sys.exit(f"nsdp_amd.train: --dataset and --synthetic {args.synthetic} were given together; choose one source of batches")
@@ -262,6 +275,10 @@ def main(argv=None):
         config = yaml.safe_load(f)
     if args.epochs is not None:
         config["training"]["epochs"] = args.epochs
+    if args.clip_grad_norm is not None:
+        config["training"]["clip_grad_norm"] = args.clip_grad_norm
+    if args.skip_nonfinite:
+        config["training"]["skip_nonfinite_steps"] = True
     os.makedirs(args.experiment_directory, exist_ok=True)
     weights = initial_weight_files(config, args)
     say = print if rank == 0 else (lambda *a, **k: None)
