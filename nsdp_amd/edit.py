@@ -1,7 +1,7 @@
 """Editing session: drag handles on a mesh without re-encoding its source.
 
     python -m nsdp_amd.edit CONFIG [--vertices N] [--surface N] [--batch B] [--part P --translate dx,dy,dz] [--drags K]
-                                   [--graph] [--weight_file F] [--out DIR]
+                                   [--graph] [--normals] [--weight_file F] [--out DIR]
     python -m nsdp_amd.edit CONFIG --vertex-counts n1,n2,... [--surface-counts s1,s2,... | --surface N] [--graph] ...
 
 The reference's interactive editing (run.py, "Interactive Editing / Run-batch-processing"; config/tosca/*.yaml,
@@ -49,6 +49,16 @@ handle set on either session class (include/nsdp_handle_sets.h): a byte per poin
     out = s.track(motions=[pose_1, ..., pose_T])                        # EditSession: T poses, one pass over T * B rows
 
     python -m nsdp_amd.edit CONFIG --handles head,frontleftfoot [--rotate-deg 20 --axis 0,0,1] [--translate dx,dy,dz] [--track T]
+
+Vertex normals of the deformed mesh, for whoever shows or exports it (nsdp_amd/mesh_normals.py, include/nsdp_meshnormals.h):
+a session opened with ``faces`` builds the mesh's corner lists once and exposes ``verts_src_normals``; ``drag / pose / track(...,
+normals=True)`` then add ``verts_tgt_normals`` (shaped as ``verts_tgt_pred``) -- two more launches behind the decode, inside
+the captured graph, a graph of its own beside the one without normals.  The predictions are the same bits either way.
+
+    s = EditSession(model, verts_src, faces=faces)       # faces [F, 3] shared by the B shapes, or [B, F, 3]
+    out = s.drag(part="head", translation=(-0.15, -0.2, -0.2), normals=True)
+
+    python -m nsdp_amd.edit CONFIG --vertices N --normals [--graph]      # a sphere mesh: the drag with and without normals
 
 Every stage of a drag is the kernel the step function runs, on the same operands: the predictions are bit-equal to
 ``test_on_batch_with_arbitrary`` (``test_on_batch_with_cano`` for a single network) on the data_dict the drag stands for
@@ -317,10 +327,11 @@ class _Session:
       _cached                                                   the attributes close() lets go of."""
 
     def __init__(self, model, verts_src, surface=None, cano=None, surface_cano=None, partial_range=0.1, cliptail=False,
-                 graph=False, max_streams=None):
+                 graph=False, max_streams=None, faces=None):
         why = self._refusal(model, verts_src, surface, cano, surface_cano)
         if why is not None:
             raise ValueError(self._refused + why)
+        self.faces = faces
         from . import query_shard
         from .model.flow_arbitrary import FlowArbitrary
         self.model = model
@@ -352,6 +363,31 @@ class _Session:
         self._open()
         return self
 
+    # ------------------------------------------------------------------ vertex normals
+    def _open_normals(self):
+        """The last step of ``_open`` (outside any capture): the topology of ``faces`` over the vertices' layout -- the corner
+        lists, one host read -- and the source mesh's normals.  Without faces the session holds neither."""
+        self.topology = self.verts_src_normals = None
+        if self.faces is not None:
+            from .mesh_normals import MeshTopology, vertex_normals
+            self.topology = MeshTopology(self.faces, self.verts)
+            self.verts_src_normals = vertex_normals(self.verts, self.topology)
+
+    def _normals_wanted(self, what, normals):
+        if normals and self.topology is None:
+            raise ValueError(self._refused + f"{what}(normals=True) without faces: the session was opened without `faces`, and "
+                             "vertex normals need the mesh's triangles -- open it with faces=...")
+        return bool(normals)
+
+    def _with_normals(self, pred, lead=None):
+        """``pred`` with the normals of its vertices: two launches behind the decode (``lead``: a track's (T, B) in front of
+        [V, 3]).  The predictions themselves are not touched."""
+        from .mesh_normals import vertex_normals
+        verts = pred["verts_tgt_pred"]
+        out = dict(pred)
+        out["verts_tgt_normals"] = vertex_normals(verts if lead is None else verts.view(lead + tuple(verts.shape[-2:])), self.topology)
+        return out
+
     # ------------------------------------------------------------------ one drag
     def _mask_buffer(self, name, like_rows, value, device):
         import torch
@@ -366,7 +402,7 @@ class _Session:
         buf.copy_(value, non_blocking=True)
 
     def drag(self, part=None, translation=(0.0, 0.0, 0.0), handle_mask=None, move_mask=None, vert_handle_mask=None,
-             vert_move_mask=None, partial_range=None, cliptail=None, with_inputs=False, clone=True):
+             vert_move_mask=None, partial_range=None, cliptail=None, with_inputs=False, clone=True, normals=False):
         """One drag of every shape.  By rule: ``part`` (a name of PARTS, one per shape, or a HandleSpec) moves by ``translation``
         ((dx, dy, dz) or [B, 3]).  By explicit regions: ``handle_mask`` / ``move_mask`` over the cloud (bool / uint8 on the GPU:
         [B, n] for a rectangular cloud, (scap,) for a packed one) replace the rule; with a separate cloud ``vert_handle_mask`` /
@@ -376,9 +412,11 @@ class _Session:
         Returns ``verts_tgt_pred``, ``surface_samples_tgt_pred``, ``verts_tgt``, ``cano_handle_vert_idx`` and
         ``cano_handle_sample_idx``, and with ``with_inputs`` ``surface_samples_inputs`` = [src | mask * tgt | mask], what the step
         function takes as it is -- shaped as the session's ``_result`` says.  The tensors are the caller's own; ``clone=False``
-        hands out the session's buffers, overwritten by the next drag."""
+        hands out the session's buffers, overwritten by the next drag.  ``normals=True`` (a session opened with ``faces``) adds
+        ``verts_tgt_normals``, the unit vertex normals of ``verts_tgt_pred`` in its shape."""
         import torch
         from ._lib import on_device
+        normals = self._normals_wanted("drag", normals)
         if torch.is_grad_enabled():
             raise ValueError(self._refused + "autograd is enabled -- drag under torch.no_grad()")
         if self.model.training:
@@ -414,9 +452,25 @@ class _Session:
                     self._mask_buffer("_vmask_h", vert_rows, vert_handle_mask, on.device)
                     self._mask_buffer("_vmask_m", vert_rows, vert_move_mask, on.device)
             key = (masks, vert_masks)
-            pred = self._dispatch(key, lambda: self._enqueue(*key))
+            pred = self._dispatch_normals(key, lambda: self._enqueue(*key), normals)
             own, own_pred = self._owners(clone)
-            return self._result(pred, own, own_pred, self.same or not masks or vert_masks, with_inputs)
+            return self._add_normals(self._result(pred, own, own_pred, self.same or not masks or vert_masks, with_inputs), pred, own_pred)
+
+    def _dispatch_normals(self, key, enqueue, normals, lead=None):
+        """``_dispatch``; with ``normals`` the vertex normals behind the same work, under a key of its own (another graph)."""
+        if not normals:
+            return self._dispatch(key, enqueue)
+        return self._dispatch(key + ("normals",), lambda: self._with_normals(enqueue(), lead))
+
+    def _add_normals(self, out, pred, own_pred, shape=None):
+        if "verts_tgt_normals" in pred:
+            n = own_pred(pred["verts_tgt_normals"])
+            out["verts_tgt_normals"] = self._over_verts(n if shape is None else n.view(shape))
+        return out
+
+    @staticmethod
+    def _over_verts(t):
+        return t
 
     def _dispatch(self, key, enqueue):
         """The GPU work of one call behind its copies: op by op, or (``graph=True``) captured at the first call of this ``key``
@@ -511,14 +565,15 @@ class _Session:
         # the vertices' own rows: with a separate cloud, when their labels are set and this form has something to move them by
         return not self.same and self._vert_labelled and (targets is None or vert_targets is not None)
 
-    def pose(self, motions=None, targets=None, vert_targets=None, with_inputs=False, clone=True):
+    def pose(self, motions=None, targets=None, vert_targets=None, with_inputs=False, clone=True, normals=False):
         """One pose of every shape's labelled handle set (``set_handles``).  ``motions``: anything ``pack_motions`` takes -- one
         list of H motions for every shape, a list per shape, or a [B, H, 12] array; one host-to-device copy.  ``targets``: a
         target per cloud point instead, a float32 GPU tensor over the cloud's layout with 3 columns ([B, n, 3]; (scap, 3)),
         read at the handle points only; ``vert_targets`` the same for the vertices of a separate cloud.  Returns what ``drag``
-        returns, in the same shapes."""
+        returns, in the same shapes (``normals=True``: with ``verts_tgt_normals``)."""
         import torch
         from ._lib import on_device
+        normals = self._normals_wanted("pose", normals)
         vert = self._pose_checks("pose", motions, targets, vert_targets)
         B, on, cloud_rows, vert_rows = self._layout()
         if targets is None:
@@ -535,9 +590,9 @@ class _Session:
                 if vert:
                     self._session_copy("_vtargets", vert_targets)
             key = ("pose", targets is not None, vert)
-            pred = self._dispatch(key, lambda: self._enqueue_pose(*key[1:]))
+            pred = self._dispatch_normals(key, lambda: self._enqueue_pose(*key[1:]), normals)
             own, own_pred = self._owners(clone)
-            return self._result(pred, own, own_pred, self.same or vert, with_inputs)
+            return self._add_normals(self._result(pred, own, own_pred, self.same or vert, with_inputs), pred, own_pred)
 
     def labels_from_parts(self, parts, verts=False):
         """Labels for ``set_handles`` from the bounding-box rule: the rule kernel runs once per named part and its ``move_out``
@@ -574,7 +629,7 @@ class _Session:
     def close(self):
         self._drop_graphs()
         self._forget_handles()
-        for name in self._cached:
+        for name in self._cached + ("topology", "verts_src_normals"):
             setattr(self, name, None)
 
     def __enter__(self):
@@ -594,7 +649,10 @@ class EditSession(_Session):
     only the index sets are cached).
 
     ``graph=True``: the first drag captures everything behind the parameter copy; later drags are copy + replay (``replays``;
-    ``eager_calls`` counts drags run op by op)."""
+    ``eager_calls`` counts drags run op by op).
+
+    ``faces``: the mesh's triangles, int32 / int64 on the GPU -- [F, 3] shared by the B shapes or [B, F, 3] -- for
+    ``verts_src_normals`` and ``normals=True`` (nsdp_amd.mesh_normals.MeshTopology: one host read at open)."""
 
     _refusal = staticmethod(refusal)
     _cached = ("geometry", "buf", "_surf_idx")
@@ -639,6 +697,7 @@ class EditSession(_Session):
                 self.verts_tgt = torch.empty((B, V, 3), dtype=torch.float32, device=dev)
                 self.verts_handle = torch.empty((B, V), dtype=torch.uint8, device=dev)
                 self._vrows = torch.empty((B, V, 7), dtype=torch.float32, device=dev)      # (the kernel's required output)
+            self._open_normals()
 
     # ------------------------------------------------------------------ one drag
     def _enqueue(self, masks, vert_masks):
@@ -722,14 +781,15 @@ class EditSession(_Session):
             pu.handle_set_rows(self.verts, self._vlabels, st.vrows, mo, vtg, tgt=st.verts_tgt, handle_out=self.verts_handle)
         return self._network(st.buf, st.geometry, st.verts2cano, st.surf2cano, st.surf_idx)
 
-    def track(self, motions=None, targets=None, vert_targets=None, with_inputs=False, clone=True):
+    def track(self, motions=None, targets=None, vert_targets=None, with_inputs=False, clone=True, normals=False):
         """T poses of the labelled handle set in one call: ``motions`` [T, B, H, 12] or a list of T ``pack_motions`` inputs, or
         ``targets`` [T, B, n, 3] on the GPU (``vert_targets`` [T, B, V, 3] for the vertices of a separate cloud).  One launch of
         the labelled kernel writes the T * B input rows, network 2 runs once over them; a drag of a small mesh is bound by its
         launches, and here the same launches carry T times the rows.
 
         Returns ``verts_tgt_pred`` and ``verts_tgt`` [T, B, V, 3], ``surface_samples_tgt_pred`` [T, B, S, 3], the handle masks
-        [B, .] (they do not depend on the pose) and with ``with_inputs`` ``surface_samples_inputs`` [T, B, S, 7].
+        [B, .] (they do not depend on the pose) and with ``with_inputs`` ``surface_samples_inputs`` [T, B, S, 7]; with
+        ``normals=True`` ``verts_tgt_normals`` [T, B, V, 3] -- the T * B poses in the same two launches.
 
         A track shares with the session network 1's outputs, the labels and the handle masks; its input rows, its index sets
         (those of the session's, over T * B rows) and its graphs -- one per (form, T) -- are its own and are made at the first
@@ -738,6 +798,7 @@ class EditSession(_Session):
         import numpy as np
         import torch
         from ._lib import on_device
+        normals = self._normals_wanted("track", normals)
         vert = self._pose_checks("track", motions, targets, vert_targets)
         B, S, V, H = self.surface.shape[0], self.surface.shape[1], self.verts.shape[1], self._count
         if targets is not None:
@@ -773,7 +834,7 @@ class EditSession(_Session):
                             setattr(st, name, torch.empty_like(value, memory_format=torch.contiguous_format))
                         getattr(st, name).copy_(value, non_blocking=True)
             key = ("track", T, targets is not None, vert)
-            pred = self._dispatch(key, lambda: self._enqueue_track(*key[1:]))
+            pred = self._dispatch_normals(key, lambda: self._enqueue_track(*key[1:]), normals, lead=(T, B))
             own, own_pred = self._owners(clone)
             have_verts = self.same or vert
             out = {"verts_tgt_pred": own_pred(pred["verts_tgt_pred"]).view(T, B, V, 3)}
@@ -786,7 +847,7 @@ class EditSession(_Session):
             if with_inputs:
                 out["surface_samples_inputs"] = torch.cat([self.surface.unsqueeze(0).expand(T, B, S, 3),
                                                            st.buf.view(T, B, S, 7)[..., 3:7]], dim=-1)
-            return out
+            return self._add_normals(out, pred, own_pred, (T, B, V, 3))
 
     def _result(self, pred, own, own_pred, have_verts, with_inputs):
         """``verts_tgt_pred`` [B, V, 3], ``surface_samples_tgt_pred`` [B, S, 3], ``verts_tgt``, ``cano_handle_vert_idx`` and
@@ -887,6 +948,9 @@ class RaggedEditSession(_Session):
     of B clouds of different sample counts, or a rectangular [B, S, 3] tensor.  ``cano`` / ``surface_cano``: the coordinates the
     bounding-box rule is evaluated on, over the layouts of ``verts_src`` / ``surface`` (None: the source coordinates).
 
+    ``faces``: a RaggedPoints of the meshes' triangles ([fcap, 3] int32 / int64 rows, indices local to their mesh) for
+    ``verts_src_normals`` and ``normals=True``; the normals come back as RaggedPoints over the vertices' offsets.
+
     The predictions are bit-equal to the step function on the ragged data_dict the drag stands for
     (tests/test_edit_session_ragged_gpu.py).  Staleness: as for EditSession -- ``reopen()`` after the weights changed."""
 
@@ -906,6 +970,9 @@ class RaggedEditSession(_Session):
             self.surface_rule = self.verts_rule if self.same else self.surface
         else:
             self.surface_rule = surface_cano.contiguous() if self.rect else tight(surface_cano)
+
+    def _over_verts(self, t):
+        return self.verts.like(t)
 
     def _layout(self):
         cloud_rows = tuple(self.surface.shape[:2]) if self.rect else (self.surface.capacity,)
@@ -960,6 +1027,7 @@ class RaggedEditSession(_Session):
                 self.verts_tgt = torch.zeros((vcap, 3), dtype=torch.float32, device=dev)
                 self.verts_handle = torch.zeros((vcap,), dtype=torch.uint8, device=dev)
                 self._vrows = torch.empty((vcap, 7), dtype=torch.float32, device=dev)      # (the kernel's required output)
+            self._open_normals()
 
     # ------------------------------------------------------------------ one drag
     def _enqueue(self, masks, vert_masks):
@@ -1166,6 +1234,9 @@ def build_parser():
     ap.add_argument("--drags", type=int, default=10, help="timed drags (each with another translation)")
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--graph", action="store_true", help="capture the drag once and replay it")
+    ap.add_argument("--normals", action="store_true",
+                    help="drag a latitude-longitude sphere (synth.sphere_mesh) of at most --vertices vertices (every count of "
+                         "--vertex-counts) and time the drag with and without the deformed mesh's vertex normals")
     ap.add_argument("--weight_file", default=None, help="weights of the whole model (default: procedural weights)")
     ap.add_argument("--out", default=None, help="directory for the last drag's predictions (<key>.npy)")
     return ap
@@ -1211,6 +1282,19 @@ def counts_from_args(args):
     return verts, surf
 
 
+def sphere_for(vertices):
+    """(verts float32 (V, 3), faces int32 (F, 3)) of the synth.sphere_mesh with the most vertices V = rings * segments + 2 <=
+    ``vertices`` among those with about twice as many segments as rings."""
+    import numpy as np
+    from . import synth
+    if vertices < 8:
+        sys.exit(f"nsdp_amd.edit: --normals wants at least 8 vertices per mesh, got {vertices}")
+    segments = max(int(np.sqrt(2.0 * (vertices - 2))), 3)
+    rings = max((vertices - 2) // segments, 2)
+    verts, faces = synth.sphere_mesh(rings, segments)
+    return verts.astype(np.float32), faces
+
+
 def _setup(args, smallest_cloud):
     """What both forms of the command line do first: the thread cap, the GPU, the config and its drag, the pyramid cut to the
     smallest cloud, the model (procedural weights without --weight_file) -- and the two helpers of the timed windows."""
@@ -1250,10 +1334,27 @@ def _setup(args, smallest_cloud):
     return device, config, spec, model, test_fn, timed, translation
 
 
+def _timed_with_normals(args, session, spec, translation, timed, warm):
+    """--normals: the same drags with ``normals=True`` (--graph: a graph of its own, captured by the first of them); None without."""
+    if not args.normals:
+        return None
+    for i in range(warm):
+        session.drag(spec.part, translation(i), normals=True)
+    return timed(lambda i: session.drag(spec.part, translation(i), clone=False, normals=True), args.drags)
+
+
+def _normals_fields(ms_drag, ms_normals, faces):
+    return {"normals": True, "faces": faces, "ms_per_drag_normals": round(ms_normals, 4),
+            "normals_ms": round(ms_normals - ms_drag, 4), "normals_over_drag": round(ms_normals / ms_drag, 4) if ms_drag > 0 else None}
+
+
 def main_ragged(args, vertex_counts, surface_counts):
     """--vertex-counts: the packed session on synthetic meshes, timed against the parent's two alternatives -- the ragged step
     function per drag, and one batch-1 EditSession per mesh dragged in turn."""
     B = len(vertex_counts)
+    spheres = [sphere_for(n) for n in vertex_counts] if args.normals else None
+    if spheres is not None:
+        vertex_counts = [int(v.shape[0]) for v, _ in spheres]
     cloud_counts = surface_counts or ([args.surface] * B if args.surface else vertex_counts)
     device, config, spec, model, test_fn, timed, translation = _setup(args, min(cloud_counts))
     import numpy as np
@@ -1261,9 +1362,13 @@ def main_ragged(args, vertex_counts, surface_counts):
     from . import pointnet2_utils, synth
     from .infer import _checksum
     from .ragged import RaggedPoints
-    meshes = [torch.from_numpy(synth.uniform(SEED_DATA + b, "mesh_verts", (1, n, 3), -0.5, 0.5)).to(device)
-              for b, n in enumerate(vertex_counts)]
+    if spheres is None:
+        meshes = [torch.from_numpy(synth.uniform(SEED_DATA + b, "mesh_verts", (1, n, 3), -0.5, 0.5)).to(device)
+                  for b, n in enumerate(vertex_counts)]
+    else:
+        meshes = [torch.from_numpy(v)[None].to(device) for v, _ in spheres]
     verts = RaggedPoints.from_list([m[0] for m in meshes])
+    faces = None if spheres is None else RaggedPoints.from_rows([torch.from_numpy(f).to(device) for _, f in spheres])
     clouds, surface = None, None
     if surface_counts is not None:
         clouds = [torch.from_numpy(synth.uniform(SEED_DATA + b, "mesh_surface", (1, n, 3), -0.5, 0.5)).to(device)
@@ -1278,13 +1383,14 @@ def main_ragged(args, vertex_counts, surface_counts):
     with torch.no_grad():
         box = {}
         timed(lambda i: box.update(s=RaggedEditSession(model, verts, surface, partial_range=spec.partial_range,
-                                                       cliptail=spec.cliptail, graph=args.graph)))      # (also packs the weights)
+                                                       cliptail=spec.cliptail, graph=args.graph, faces=faces)))      # (also packs the weights)
         session = box["s"]
         ms_open = timed(lambda i: session.reopen())
         out = {}
         for i in range(warm):      # (--graph: the first drag captures)
             session.drag(spec.part, translation(i))
         ms_drag = timed(lambda i: out.update(session.drag(spec.part, translation(i), clone=False)), args.drags)
+        ms_normals = _timed_with_normals(args, session, spec, translation, timed, warm)
         out = session.drag(spec.part, translation(args.drags - 1), with_inputs=True)
         inputs = out["surface_samples_inputs"]
         dd = {"surface_samples_inputs": inputs, "verts_src": verts,
@@ -1320,6 +1426,8 @@ def main_ragged(args, vertex_counts, surface_counts):
             "per_mesh_sessions_over_drag": round(ms_singles / ms_drag, 3) if ms_drag > 0 else None,
             "replays": session.replays, "eager_calls": session.eager_calls, "equal_to_full_call": bool(equal),
             "checksum": _checksum(packed(out["verts_tgt_pred"]))}
+    if args.normals:
+        line.update(_normals_fields(ms_drag, ms_normals, sum(int(f.shape[0]) for _, f in spheres)))
     print(json.dumps(line), flush=True)
     session.close()
     return 0
@@ -1415,6 +1523,8 @@ def main(argv=None):
     vertex_counts, surface_counts = counts_from_args(args)
     names, axis = handles_from_args(args)
     if names is not None:
+        if args.normals:
+            sys.exit("nsdp_amd.edit: --normals times drags by rule (--part), not --handles")
         if vertex_counts is not None:
             sys.exit("nsdp_amd.edit: --handles goes with --vertices / --batch, not with --vertex-counts")
         if args.vertices < 1 or (args.surface is not None and args.surface < 1) or args.drags < 1:
@@ -1426,25 +1536,33 @@ def main(argv=None):
         return main_ragged(args, vertex_counts, surface_counts)
     if args.vertices < 1 or (args.surface is not None and args.surface < 1) or args.drags < 1:
         sys.exit("nsdp_amd.edit: --vertices, --surface and --drags want positive integers")
+    sphere = sphere_for(args.vertices) if args.normals else None
+    if sphere is not None:
+        args.vertices = int(sphere[0].shape[0])
     device, config, spec, model, test_fn, timed, translation = _setup(args, args.surface or args.vertices)
     import numpy as np
     import torch
     from . import pointnet2_utils, synth
     from .infer import _checksum
     batch = args.batch or int((config.get("test") or {}).get("batch_size", 1) or 1)
-    verts = torch.from_numpy(synth.uniform(SEED_DATA, "mesh_verts", (batch, args.vertices, 3), -0.5, 0.5)).to(device)
+    if sphere is None:
+        verts, faces = torch.from_numpy(synth.uniform(SEED_DATA, "mesh_verts", (batch, args.vertices, 3), -0.5, 0.5)).to(device), None
+    else:
+        verts = torch.from_numpy(sphere[0])[None].repeat(batch, 1, 1).to(device)
+        faces = torch.from_numpy(sphere[1]).to(device)
     surface = None if args.surface is None else \
         torch.from_numpy(synth.uniform(SEED_DATA, "mesh_surface", (batch, args.surface, 3), -0.5, 0.5)).to(device)
     with torch.no_grad():
         box = {}
         timed(lambda i: box.update(s=EditSession(model, verts, surface, partial_range=spec.partial_range, cliptail=spec.cliptail,
-                                                 graph=args.graph)))      # (the first open also packs the weights)
+                                                 graph=args.graph, faces=faces)))      # (the first open also packs the weights)
         session = box["s"]
         ms_open = timed(lambda i: session.reopen())
         out = {}
         for i in range(max(args.warmup, 1)):      # (--graph: the first drag captures)
             session.drag(spec.part, translation(i))
         ms_drag = timed(lambda i: out.update(session.drag(spec.part, translation(i), clone=False)), args.drags)
+        ms_normals = _timed_with_normals(args, session, spec, translation, timed, max(args.warmup, 1))
         out = session.drag(spec.part, translation(args.drags - 1), with_inputs=True)
         dd = {"surface_samples_inputs": out["surface_samples_inputs"], "verts_src": verts,
               "surface_samples_src": out["surface_samples_inputs"][:, :, 0:3].contiguous()}
@@ -1466,6 +1584,8 @@ def main(argv=None):
             "full_call_over_drag": round(ms_full / ms_drag, 3) if ms_drag > 0 else None,
             "replays": session.replays, "eager_calls": session.eager_calls, "equal_to_full_call": bool(equal),
             "checksum": _checksum(out["verts_tgt_pred"])}
+    if args.normals:
+        line.update(_normals_fields(ms_drag, ms_normals, int(sphere[1].shape[0])))
     print(json.dumps(line), flush=True)
     session.close()
     return 0

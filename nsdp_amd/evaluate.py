@@ -29,6 +29,13 @@ compute_l2_error); at ``--batch 1`` it is the pair's own, as in the reference.
 ``HandleSpec.from_config(config["data"])``, exports the source, deformed, target and handle meshes into a folder named after the
 drag (``drag_folder_name``), and computes no metrics.
 
+Vertex normals, opt-in (nsdp_amd/mesh_normals.py; with neither key the files are byte for byte what they were):
+  test.export_normals: true               the source, deformed and target meshes are written with per-vertex normals computed on
+                                          the device -- the three vertex sets as three poses of the batch's one topology -- which
+                                          travel in the batch's ONE device-to-host copy;
+  test.vertex_normal_consistency: true    adds ``vnc`` to every pair: the mean over the vertices of |n_pred . n_gt|
+                                          (``vertex_normal_consistency``), in the .txt, the .json and the batch's one ``.tolist()``.
+
 Refused by name: ``test.generate_pointcloud`` (point-cloud export).  Out of scope: ``--gpus N``, graph replay of the whole step.
 """
 from __future__ import annotations
@@ -110,10 +117,40 @@ def _to_host(vertex_sets, handle, faces):
     return out, flat[at:at + cap].astype(bool), flat[at + cap:].reshape(-1, 3)
 
 
-def export_meshes(directory, pair_infos, ext, verts, handle, faces, vert_counts, face_counts):
+def batch_normals(faces, vertex_sets):
+    """Unit vertex normals [P, cap, 3] of P vertex sets (RaggedPoints over one layout) that share the packed topology ``faces``
+    (a RaggedPoints of int32 rows): the corner lists once, two launches for all P.  The store has clamped every face index
+    into its mesh, so nothing is read back to validate them."""
+    from .mesh_normals import MeshTopology, vertex_normals
+    topology = MeshTopology(faces, vertex_sets[0], validate=False)
+    return vertex_normals(torch.stack([v.packed.detach() for v in vertex_sets]), topology)
+
+
+def vertex_normal_consistency(n_pred, n_gt, offsets):
+    """[B] float64: per shape the mean over its vertices of |n_pred . n_gt| -- 1 where the predicted surface is oriented like
+    the target's everywhere, in [0, 1] always.  ``n_pred`` / ``n_gt`` [cap, 3] fp32 unit normals (zeros where a vertex has
+    none), ``offsets`` the vertices' [B + 1] int32.  The dot is fp32, ((x x' + y y') + z z'); the mean goes through
+    nsdp_segment_mean_f32 -- double accumulation in a fixed order, one fp32 result per shape -- three times: the mean m, then
+    the means of the two fp32 halves of the residuals v - m (formed in double), which are ~2^-24 of m's size, so that their own
+    fp32 roundings fall below 1e-14.  m + the two corrections, added in double, is the double-precision mean of the fp32 dots."""
+    from .eval_metric import _dot_rows
+    from .pointnet2_utils import segment_mean
+    from .ragged import shape_ids
+    B = int(offsets.numel()) - 1
+    v = _dot_rows(n_pred, n_gt).abs().contiguous()
+    m = segment_mean(v, offsets).double()
+    r = v.double() - m[shape_ids(offsets, int(v.shape[0])).clamp(max=B - 1)]
+    hi = r.float()
+    lo = (r - hi.double()).float()
+    return (m + segment_mean(hi, offsets).double()) + segment_mean(lo, offsets).double()
+
+
+def export_meshes(directory, pair_infos, ext, verts, handle, faces, vert_counts, face_counts, normals=None):
     """Write the meshes of a batch that is already on the host.  ``verts``: part -> [cap, 3] fp32 for "source", "deformed",
-    "target" and, where it is exported, "canonical"; ``handle`` [cap] bool; ``faces`` [fcap, 3] int32, local indices."""
+    "target" and, where it is exported, "canonical"; ``handle`` [cap] bool; ``faces`` [fcap, 3] int32, local indices;
+    ``normals``: part -> [cap, 3] fp32 for the parts that are written with normals."""
     from .meshio import write_mesh
+    normals = normals or {}
     v0 = f0 = 0
     for info, nv, nf in zip(pair_infos, vert_counts, face_counts):
         names = export_names(info, ext)
@@ -126,7 +163,10 @@ def export_meshes(directory, pair_infos, ext, verts, handle, faces, vert_counts,
                 continue
             path = os.path.join(directory, names[part])
             os.makedirs(os.path.dirname(path), exist_ok=True)
-            write_mesh(path, verts[of][v0:v0 + nv], sel, colors)
+            if normals.get(part) is None:
+                write_mesh(path, verts[of][v0:v0 + nv], sel, colors)
+            else:
+                write_mesh(path, verts[of][v0:v0 + nv], sel, colors, normals[part][v0:v0 + nv])
         v0, f0 = v0 + nv, f0 + nf
 
 
@@ -149,6 +189,8 @@ def evaluate(model, test_fn, store, config, experiment_directory, batch, seed, l
     split = test.get("motion_split", store.motion_split)
     mesh_dir = os.path.join(experiment_directory, split, test.get("mesh_folder", "meshes")) if test.get("generate_mesh") else None
     ext = test.get("mesh_format", "ply")
+    with_normals, with_vnc = bool(test.get("export_normals")) and mesh_dir is not None, bool(test.get("vertex_normal_consistency"))
+    metrics = METRICS + (("vnc",) if with_vnc else ())
     rows = []
     with open(os.path.join(experiment_directory, split + ".txt"), "w") as txt:
         def say(line):
@@ -159,22 +201,29 @@ def evaluate(model, test_fn, store, config, experiment_directory, batch, seed, l
             pred, faces = out["verts_tgt_pred"], out["faces"]
             samples = metric_samples(pred, faces, test.get("pointcloud_size", 30000), seed, step)
             m = compute_evaluation_metrics_batch(out, samples=samples)
-            values = torch.stack([m[k] for k in METRICS]).tolist()      # the batch's ONE read-back of metrics
+            if with_normals or with_vnc:
+                n_pred, n_tgt, n_src = batch_normals(faces, [pred, out["verts_tgt"], out["verts_src"]])
+            if with_vnc:
+                m["vnc"] = vertex_normal_consistency(n_pred, n_tgt, pred.offsets)
+                values = torch.stack([m[k].double() for k in metrics]).tolist()      # (fp32 -> double is exact: the same numbers)
+            else:
+                values = torch.stack([m[k] for k in METRICS]).tolist()      # the batch's ONE read-back of metrics
             infos = [store.pairs[i] for i in out["index"]]
             for b, info in enumerate(infos):
                 row = {"index": int(out["index"][b]), "pair_info": list(info), "loss": float(loss)}
-                row.update({k: values[c][b] for c, k in enumerate(METRICS)})
+                row.update({k: values[c][b] for c, k in enumerate(metrics)})
                 rows.append(row)
                 say("pair {:5d} {}_{} -> {}_{}  loss {:.6e}  ".format(row["index"], info[4], info[5], info[6], info[7], row["loss"])
-                    + "  ".join("{} {:.6e}".format(k, row[k]) for k in METRICS))
+                    + "  ".join("{} {:.6e}".format(k, row[k]) for k in metrics))
             if mesh_dir is not None:
+                extra = [n_src, n_pred, n_tgt] if with_normals else []      # (in the same copy)
                 sets, handle, f = _to_host([out["verts_src"].packed, out["verts_cano"].packed, pred.packed.detach(),
-                                            out["verts_tgt"].packed], out["cano_handle_vert_idx"], faces.packed)
+                                            out["verts_tgt"].packed] + extra, out["cano_handle_vert_idx"], faces.packed)
                 export_meshes(mesh_dir, infos, ext, dict(zip(("source", "canonical", "deformed", "target"), sets)), handle, f,
-                              pred.counts, faces.counts)
-        means, left_out = filtered_means(rows)
-        say("mean over {} pairs (values <= 1.0 only)  ".format(len(rows)) + "  ".join("{} {:.6e}".format(k, means[k]) for k in METRICS)
-            + "  left out: " + ", ".join("{} {}".format(k, left_out[k]) for k in METRICS))
+                              pred.counts, faces.counts, dict(zip(("source", "deformed", "target"), sets[4:])))
+        means, left_out = filtered_means(rows, metrics)
+        say("mean over {} pairs (values <= 1.0 only)  ".format(len(rows)) + "  ".join("{} {:.6e}".format(k, means[k]) for k in metrics)
+            + "  left out: " + ", ".join("{} {}".format(k, left_out[k]) for k in metrics))
     with open(os.path.join(experiment_directory, split + ".json"), "w") as f:
         json.dump({"pairs": rows, "means": means, "left_out": left_out}, f, indent=1)
     return rows
@@ -195,9 +244,11 @@ def _drag_loop(model, store, loader, config, experiment_directory, log):
             out = session.drag(spec)
             infos = [store.pairs[i] for i in data_dict["index"]]
             if test.get("generate_mesh", True):
-                sets, handle, f = _to_host([src.packed, out["verts_tgt_pred"].packed, out["verts_tgt"].packed],
-                                           out["cano_handle_vert_idx"].packed, faces.packed)
-                export_meshes(mesh_dir, infos, ext, dict(zip(("source", "deformed", "target"), sets)), handle, f, src.counts, faces.counts)
+                parts = [src, out["verts_tgt_pred"], out["verts_tgt"]]
+                extra = list(batch_normals(faces, parts)) if test.get("export_normals") else []      # (in the same copy)
+                sets, handle, f = _to_host([p.packed for p in parts] + extra, out["cano_handle_vert_idx"].packed, faces.packed)
+                export_meshes(mesh_dir, infos, ext, dict(zip(("source", "deformed", "target"), sets)), handle, f, src.counts,
+                              faces.counts, dict(zip(("source", "deformed", "target"), sets[3:])))
         for i, info in zip(data_dict["index"], infos):
             rows.append({"index": int(i), "pair_info": list(info)})
             log("dragged {} ({}) -> {}".format(info[4], spec.part, os.path.join(mesh_dir, export_names(info, ext)["deformed"])))

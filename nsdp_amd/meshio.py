@@ -18,9 +18,11 @@ file go through ONE numpy conversion, no ``float()`` per line: a data set is tho
 ``MeshError`` (a ValueError) names the file and the reason: a vertex index outside [0, V), a face of fewer than three corners,
 no vertices or no faces, an unknown extension, a file that ends early.
 
-``write_mesh(path, verts, faces, colors=None)``: .obj (text, 1-based) and binary little-endian .ply (float32 vertices as
-``float``, others as ``double``; int32 faces), with per-vertex uint8 RGB where given -- so that a round trip can be tested and
-predictions written.
+``write_mesh(path, verts, faces, colors=None, normals=None)``: .obj (text, 1-based) and binary little-endian .ply (float32
+vertices as ``float``, others as ``double``; int32 faces), with per-vertex uint8 RGB where given -- so that a round trip can be
+tested and predictions written.  Per-vertex ``normals`` (V, 3) become ``nx ny nz`` properties behind ``x y z`` in the vertex
+type (.ply) and ``vn`` statements with ``f a//a b//b c//c`` corners (.obj); ``read_mesh`` reads such a file back to the same
+vertices and faces (it skips further properties and what follows a corner's slash).
 """
 from __future__ import annotations
 
@@ -277,8 +279,9 @@ def read_mesh(path):
 
 
 # ---------------------------------------------------------------------------------------------------------------- writer
-def write_mesh(path, verts, faces, colors=None):
-    """Write (verts (V, 3) float, faces (F, 3) int[, colors (V, 3) uint8]) as .obj or binary little-endian .ply."""
+def write_mesh(path, verts, faces, colors=None, normals=None):
+    """Write (verts (V, 3) float, faces (F, 3) int[, colors (V, 3) uint8][, normals (V, 3) float]) as .obj or binary
+    little-endian .ply."""
     path = os.fspath(path)
     ext = os.path.splitext(path)[1].lower()
     verts = np.asarray(verts)
@@ -291,6 +294,11 @@ def write_mesh(path, verts, faces, colors=None):
         colors = np.asarray(colors)
         if colors.shape != verts.shape or colors.dtype != np.uint8:
             raise MeshError(f"write_mesh: {path}: colors must be uint8 {verts.shape}, got {colors.dtype} {colors.shape}")
+    if normals is not None:
+        normals = np.asarray(normals)
+        if normals.shape != verts.shape or normals.dtype.kind != "f":
+            raise MeshError(f"write_mesh: {path}: normals must be float {verts.shape}, got {normals.dtype} {normals.shape}")
+        normals = normals.astype(verts.dtype)                                # (the vertex type)
     if ext == ".obj":
         digits = "%.9g" if verts.dtype == np.float32 else "%.17g"            # (enough to read the same binary number back)
         with open(path, "w") as f:
@@ -298,13 +306,21 @@ def write_mesh(path, verts, faces, colors=None):
                 np.savetxt(f, verts, fmt="v " + " ".join([digits] * 3))
             else:
                 np.savetxt(f, np.concatenate([verts.astype(np.float64), colors / 255.0], axis=1), fmt="v " + " ".join([digits] * 3 + ["%.6g"] * 3))
-            np.savetxt(f, faces.astype(np.int64) + 1, fmt="f %d %d %d")
+            if normals is None:
+                np.savetxt(f, faces.astype(np.int64) + 1, fmt="f %d %d %d")
+            else:
+                np.savetxt(f, normals, fmt="vn " + " ".join([digits] * 3))
+                np.savetxt(f, np.repeat(faces.astype(np.int64) + 1, 2, axis=1), fmt="f %d//%d %d//%d %d//%d")
     elif ext == ".ply":
         real = "float" if verts.dtype == np.float32 else "double"
-        fields = [(a, "<" + _PLY_TYPES[real]) for a in "xyz"] + ([(c, "u1") for c in ("red", "green", "blue")] if colors is not None else [])
+        fields = [(a, "<" + _PLY_TYPES[real]) for a in "xyz"] + ([(a, "<" + _PLY_TYPES[real]) for a in ("nx", "ny", "nz")] if normals is not None else [])
+        fields += ([(c, "u1") for c in ("red", "green", "blue")] if colors is not None else [])
         vrec = np.empty(verts.shape[0], dtype=np.dtype(fields))
         for k, a in enumerate("xyz"):
             vrec[a] = verts[:, k]
+        if normals is not None:
+            for k, a in enumerate(("nx", "ny", "nz")):
+                vrec[a] = normals[:, k]
         if colors is not None:
             for k, c in enumerate(("red", "green", "blue")):
                 vrec[c] = colors[:, k]
@@ -312,6 +328,7 @@ def write_mesh(path, verts, faces, colors=None):
         frec["n"], frec["i"] = 3, faces
         header = ["ply", "format binary_little_endian 1.0", f"element vertex {verts.shape[0]}"]
         header += [f"property {real} {a}" for a in "xyz"]
+        header += [f"property {real} {a}" for a in ("nx", "ny", "nz")] if normals is not None else []
         header += [f"property uchar {c}" for c in ("red", "green", "blue")] if colors is not None else []
         header += [f"element face {faces.shape[0]}", "property list uchar int vertex_indices", "end_header"]
         with open(path, "wb") as f:
