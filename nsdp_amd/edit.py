@@ -1,7 +1,7 @@
 """Editing session: drag handles on a mesh without re-encoding its source.
 
     python -m nsdp_amd.edit CONFIG [--vertices N] [--surface N] [--batch B] [--part P --translate dx,dy,dz] [--drags K]
-                                   [--graph] [--normals] [--weight_file F] [--out DIR]
+                                   [--graph] [--normals] [--self-intersections] [--weight_file F] [--out DIR]
     python -m nsdp_amd.edit CONFIG --vertex-counts n1,n2,... [--surface-counts s1,s2,... | --surface N] [--graph] ...
 
 The reference's interactive editing (run.py, "Interactive Editing / Run-batch-processing"; config/tosca/*.yaml,
@@ -59,6 +59,13 @@ the captured graph, a graph of its own beside the one without normals.  The pred
     out = s.drag(part="head", translation=(-0.15, -0.2, -0.2), normals=True)
 
     python -m nsdp_amd.edit CONFIG --vertices N --normals [--graph]      # a sphere mesh: the drag with and without normals
+
+Self-intersections of the deformed mesh (nsdp_amd/self_intersect.py, include/nsdp_selfintersect.h): with ``faces``,
+``drag / pose / track(..., self_intersections=True)`` add ``faces_tgt_hits`` (per face the faces it passes through; -1: skipped
+by the work guard), ``tgt_self_intersections`` (the intersecting pairs of every mesh, of every pose and mesh for a track) and
+``tgt_self_skipped`` -- behind the decode, inside a captured graph of its own; the predictions are the same bits either way.
+
+    python -m nsdp_amd.edit CONFIG --vertices N --self-intersections [--graph]      # the counts of every drag, and its time
 
 Every stage of a drag is the kernel the step function runs, on the same operands: the predictions are bit-equal to
 ``test_on_batch_with_arbitrary`` (``test_on_batch_with_cano`` for a single network) on the data_dict the drag stands for
@@ -367,7 +374,7 @@ class _Session:
     def _open_normals(self):
         """The last step of ``_open`` (outside any capture): the topology of ``faces`` over the vertices' layout -- the corner
         lists, one host read -- and the source mesh's normals.  Without faces the session holds neither."""
-        self.topology = self.verts_src_normals = None
+        self.topology = self.verts_src_normals = self.selfint_plan = None
         if self.faces is not None:
             from .mesh_normals import MeshTopology, vertex_normals
             self.topology = MeshTopology(self.faces, self.verts)
@@ -378,6 +385,27 @@ class _Session:
             raise ValueError(self._refused + f"{what}(normals=True) without faces: the session was opened without `faces`, and "
                              "vertex normals need the mesh's triangles -- open it with faces=...")
         return bool(normals)
+
+    def _selfint_wanted(self, what, wanted):
+        """``self_intersections=True`` needs the faces; the plan (the faces in Morton order of the source mesh, no host read:
+        the topology is validated) is made at the first such call, outside any capture."""
+        if wanted and self.topology is None:
+            raise ValueError(self._refused + f"{what}(self_intersections=True) without faces: the session was opened without "
+                             "`faces`, and self-intersections are between the mesh's triangles -- open it with faces=...")
+        if wanted and self.selfint_plan is None:
+            from .self_intersect import SelfIntersectionPlan
+            self.selfint_plan = SelfIntersectionPlan(self.faces, self.verts, topology=self.topology)
+        return bool(wanted)
+
+    def _with_self_intersections(self, pred, lead=None):
+        """``pred`` with the self-intersections of its vertices (nsdp_amd/self_intersect.py): the entry's launches behind the
+        decode.  The predictions themselves are not touched."""
+        from .self_intersect import self_intersections
+        verts = pred["verts_tgt_pred"]
+        r = self_intersections(verts if lead is None else verts.view(lead + tuple(verts.shape[-2:])), self.selfint_plan)
+        out = dict(pred)
+        out["faces_tgt_hits"], out["tgt_self_intersections"], out["tgt_self_skipped"] = r.hits, r.pairs, r.skipped
+        return out
 
     def _with_normals(self, pred, lead=None):
         """``pred`` with the normals of its vertices: two launches behind the decode (``lead``: a track's (T, B) in front of
@@ -402,7 +430,8 @@ class _Session:
         buf.copy_(value, non_blocking=True)
 
     def drag(self, part=None, translation=(0.0, 0.0, 0.0), handle_mask=None, move_mask=None, vert_handle_mask=None,
-             vert_move_mask=None, partial_range=None, cliptail=None, with_inputs=False, clone=True, normals=False):
+             vert_move_mask=None, partial_range=None, cliptail=None, with_inputs=False, clone=True, normals=False,
+             self_intersections=False):
         """One drag of every shape.  By rule: ``part`` (a name of PARTS, one per shape, or a HandleSpec) moves by ``translation``
         ((dx, dy, dz) or [B, 3]).  By explicit regions: ``handle_mask`` / ``move_mask`` over the cloud (bool / uint8 on the GPU:
         [B, n] for a rectangular cloud, (scap,) for a packed one) replace the rule; with a separate cloud ``vert_handle_mask`` /
@@ -413,10 +442,14 @@ class _Session:
         ``cano_handle_sample_idx``, and with ``with_inputs`` ``surface_samples_inputs`` = [src | mask * tgt | mask], what the step
         function takes as it is -- shaped as the session's ``_result`` says.  The tensors are the caller's own; ``clone=False``
         hands out the session's buffers, overwritten by the next drag.  ``normals=True`` (a session opened with ``faces``) adds
-        ``verts_tgt_normals``, the unit vertex normals of ``verts_tgt_pred`` in its shape."""
+        ``verts_tgt_normals``, the unit vertex normals of ``verts_tgt_pred`` in its shape.  ``self_intersections=True`` (faces
+        too) adds ``faces_tgt_hits`` (per face the faces it passes through, -1: skipped by the work guard),
+        ``tgt_self_intersections`` (int64, the intersecting pairs of every mesh) and ``tgt_self_skipped`` -- the fields of
+        ``nsdp_amd.self_intersect.self_intersections`` on ``verts_tgt_pred``."""
         import torch
         from ._lib import on_device
         normals = self._normals_wanted("drag", normals)
+        selfint = self._selfint_wanted("drag", self_intersections)
         if torch.is_grad_enabled():
             raise ValueError(self._refused + "autograd is enabled -- drag under torch.no_grad()")
         if self.model.training:
@@ -452,20 +485,30 @@ class _Session:
                     self._mask_buffer("_vmask_h", vert_rows, vert_handle_mask, on.device)
                     self._mask_buffer("_vmask_m", vert_rows, vert_move_mask, on.device)
             key = (masks, vert_masks)
-            pred = self._dispatch_normals(key, lambda: self._enqueue(*key), normals)
+            pred = self._dispatch_normals(key, lambda: self._enqueue(*key), normals, selfint=selfint)
             own, own_pred = self._owners(clone)
             return self._add_normals(self._result(pred, own, own_pred, self.same or not masks or vert_masks, with_inputs), pred, own_pred)
 
-    def _dispatch_normals(self, key, enqueue, normals, lead=None):
-        """``_dispatch``; with ``normals`` the vertex normals behind the same work, under a key of its own (another graph)."""
-        if not normals:
+    def _dispatch_normals(self, key, enqueue, normals, lead=None, selfint=False):
+        """``_dispatch``; with ``normals`` the vertex normals behind the same work, with ``selfint`` the self-intersections,
+        each under a key of its own (another graph): calls without the flags keep their graph and their bits."""
+        if not normals and not selfint:
             return self._dispatch(key, enqueue)
-        return self._dispatch(key + ("normals",), lambda: self._with_normals(enqueue(), lead))
+
+        def work():
+            pred = enqueue()
+            if normals:
+                pred = self._with_normals(pred, lead)
+            return self._with_self_intersections(pred, lead) if selfint else pred
+        return self._dispatch(key + (("normals",) if normals else ()) + (("self_intersections",) if selfint else ()), work)
 
     def _add_normals(self, out, pred, own_pred, shape=None):
         if "verts_tgt_normals" in pred:
             n = own_pred(pred["verts_tgt_normals"])
             out["verts_tgt_normals"] = self._over_verts(n if shape is None else n.view(shape))
+        for name in ("faces_tgt_hits", "tgt_self_intersections", "tgt_self_skipped"):
+            if name in pred:
+                out[name] = own_pred(pred[name])
         return out
 
     @staticmethod
@@ -565,15 +608,18 @@ class _Session:
         # the vertices' own rows: with a separate cloud, when their labels are set and this form has something to move them by
         return not self.same and self._vert_labelled and (targets is None or vert_targets is not None)
 
-    def pose(self, motions=None, targets=None, vert_targets=None, with_inputs=False, clone=True, normals=False):
+    def pose(self, motions=None, targets=None, vert_targets=None, with_inputs=False, clone=True, normals=False,
+             self_intersections=False):
         """One pose of every shape's labelled handle set (``set_handles``).  ``motions``: anything ``pack_motions`` takes -- one
         list of H motions for every shape, a list per shape, or a [B, H, 12] array; one host-to-device copy.  ``targets``: a
         target per cloud point instead, a float32 GPU tensor over the cloud's layout with 3 columns ([B, n, 3]; (scap, 3)),
         read at the handle points only; ``vert_targets`` the same for the vertices of a separate cloud.  Returns what ``drag``
-        returns, in the same shapes (``normals=True``: with ``verts_tgt_normals``)."""
+        returns, in the same shapes (``normals=True``: with ``verts_tgt_normals``; ``self_intersections=True``: with ``drag``'s
+        three fields)."""
         import torch
         from ._lib import on_device
         normals = self._normals_wanted("pose", normals)
+        selfint = self._selfint_wanted("pose", self_intersections)
         vert = self._pose_checks("pose", motions, targets, vert_targets)
         B, on, cloud_rows, vert_rows = self._layout()
         if targets is None:
@@ -590,7 +636,7 @@ class _Session:
                 if vert:
                     self._session_copy("_vtargets", vert_targets)
             key = ("pose", targets is not None, vert)
-            pred = self._dispatch_normals(key, lambda: self._enqueue_pose(*key[1:]), normals)
+            pred = self._dispatch_normals(key, lambda: self._enqueue_pose(*key[1:]), normals, selfint=selfint)
             own, own_pred = self._owners(clone)
             return self._add_normals(self._result(pred, own, own_pred, self.same or vert, with_inputs), pred, own_pred)
 
@@ -629,7 +675,7 @@ class _Session:
     def close(self):
         self._drop_graphs()
         self._forget_handles()
-        for name in self._cached + ("topology", "verts_src_normals"):
+        for name in self._cached + ("topology", "verts_src_normals", "selfint_plan"):
             setattr(self, name, None)
 
     def __enter__(self):
@@ -781,7 +827,8 @@ class EditSession(_Session):
             pu.handle_set_rows(self.verts, self._vlabels, st.vrows, mo, vtg, tgt=st.verts_tgt, handle_out=self.verts_handle)
         return self._network(st.buf, st.geometry, st.verts2cano, st.surf2cano, st.surf_idx)
 
-    def track(self, motions=None, targets=None, vert_targets=None, with_inputs=False, clone=True, normals=False):
+    def track(self, motions=None, targets=None, vert_targets=None, with_inputs=False, clone=True, normals=False,
+              self_intersections=False):
         """T poses of the labelled handle set in one call: ``motions`` [T, B, H, 12] or a list of T ``pack_motions`` inputs, or
         ``targets`` [T, B, n, 3] on the GPU (``vert_targets`` [T, B, V, 3] for the vertices of a separate cloud).  One launch of
         the labelled kernel writes the T * B input rows, network 2 runs once over them; a drag of a small mesh is bound by its
@@ -789,7 +836,8 @@ class EditSession(_Session):
 
         Returns ``verts_tgt_pred`` and ``verts_tgt`` [T, B, V, 3], ``surface_samples_tgt_pred`` [T, B, S, 3], the handle masks
         [B, .] (they do not depend on the pose) and with ``with_inputs`` ``surface_samples_inputs`` [T, B, S, 7]; with
-        ``normals=True`` ``verts_tgt_normals`` [T, B, V, 3] -- the T * B poses in the same two launches.
+        ``normals=True`` ``verts_tgt_normals`` [T, B, V, 3] -- the T * B poses in the same two launches; with
+        ``self_intersections=True`` ``faces_tgt_hits`` [T, B, F], ``tgt_self_intersections`` and ``tgt_self_skipped`` [T, B].
 
         A track shares with the session network 1's outputs, the labels and the handle masks; its input rows, its index sets
         (those of the session's, over T * B rows) and its graphs -- one per (form, T) -- are its own and are made at the first
@@ -799,6 +847,7 @@ class EditSession(_Session):
         import torch
         from ._lib import on_device
         normals = self._normals_wanted("track", normals)
+        selfint = self._selfint_wanted("track", self_intersections)
         vert = self._pose_checks("track", motions, targets, vert_targets)
         B, S, V, H = self.surface.shape[0], self.surface.shape[1], self.verts.shape[1], self._count
         if targets is not None:
@@ -834,7 +883,7 @@ class EditSession(_Session):
                             setattr(st, name, torch.empty_like(value, memory_format=torch.contiguous_format))
                         getattr(st, name).copy_(value, non_blocking=True)
             key = ("track", T, targets is not None, vert)
-            pred = self._dispatch_normals(key, lambda: self._enqueue_track(*key[1:]), normals, lead=(T, B))
+            pred = self._dispatch_normals(key, lambda: self._enqueue_track(*key[1:]), normals, lead=(T, B), selfint=selfint)
             own, own_pred = self._owners(clone)
             have_verts = self.same or vert
             out = {"verts_tgt_pred": own_pred(pred["verts_tgt_pred"]).view(T, B, V, 3)}
@@ -1237,6 +1286,9 @@ def build_parser():
     ap.add_argument("--normals", action="store_true",
                     help="drag a latitude-longitude sphere (synth.sphere_mesh) of at most --vertices vertices (every count of "
                          "--vertex-counts) and time the drag with and without the deformed mesh's vertex normals")
+    ap.add_argument("--self-intersections", action="store_true", dest="self_intersections",
+                    help="drag the sphere mesh of --normals and print, per drag, the intersecting face pairs of every deformed "
+                         "mesh (self_intersections=True), and the drag's time with them")
     ap.add_argument("--weight_file", default=None, help="weights of the whole model (default: procedural weights)")
     ap.add_argument("--out", default=None, help="directory for the last drag's predictions (<key>.npy)")
     return ap
@@ -1343,6 +1395,26 @@ def _timed_with_normals(args, session, spec, translation, timed, warm):
     return timed(lambda i: session.drag(spec.part, translation(i), clone=False, normals=True), args.drags)
 
 
+def _timed_with_self_intersections(args, session, spec, translation, timed, warm):
+    """--self-intersections: the same drags with ``self_intersections=True`` (--graph: a graph of its own) -> the JSON fields:
+    the time, and per drag the intersecting pairs, the faces with a hit and the faces the work guard skipped of every mesh."""
+    import torch
+    if not args.self_intersections:
+        return {}
+    for i in range(warm):
+        session.drag(spec.part, translation(i), self_intersections=True)
+    ms = timed(lambda i: session.drag(spec.part, translation(i), clone=False, self_intersections=True), args.drags)
+    rows = []
+    for i in range(args.drags):
+        out = session.drag(spec.part, translation(i), self_intersections=True)
+        rows.append(torch.stack([out["tgt_self_intersections"].reshape(-1), out["tgt_self_skipped"].reshape(-1).long()]))
+    counts = torch.stack(rows).tolist()      # (one read for all drags)
+    for i, (pairs, skipped) in enumerate(counts):
+        print(f"drag {i}: self-intersecting face pairs per mesh {pairs}, faces skipped by the guard {skipped}", flush=True)
+    return {"self_intersections": True, "ms_per_drag_self_intersections": round(ms, 4),
+            "self_intersection_pairs": [c[0] for c in counts], "self_intersection_skipped": [c[1] for c in counts]}
+
+
 def _normals_fields(ms_drag, ms_normals, faces):
     return {"normals": True, "faces": faces, "ms_per_drag_normals": round(ms_normals, 4),
             "normals_ms": round(ms_normals - ms_drag, 4), "normals_over_drag": round(ms_normals / ms_drag, 4) if ms_drag > 0 else None}
@@ -1352,7 +1424,7 @@ def main_ragged(args, vertex_counts, surface_counts):
     """--vertex-counts: the packed session on synthetic meshes, timed against the parent's two alternatives -- the ragged step
     function per drag, and one batch-1 EditSession per mesh dragged in turn."""
     B = len(vertex_counts)
-    spheres = [sphere_for(n) for n in vertex_counts] if args.normals else None
+    spheres = [sphere_for(n) for n in vertex_counts] if args.normals or args.self_intersections else None
     if spheres is not None:
         vertex_counts = [int(v.shape[0]) for v, _ in spheres]
     cloud_counts = surface_counts or ([args.surface] * B if args.surface else vertex_counts)
@@ -1391,6 +1463,7 @@ def main_ragged(args, vertex_counts, surface_counts):
             session.drag(spec.part, translation(i))
         ms_drag = timed(lambda i: out.update(session.drag(spec.part, translation(i), clone=False)), args.drags)
         ms_normals = _timed_with_normals(args, session, spec, translation, timed, warm)
+        selfint_fields = _timed_with_self_intersections(args, session, spec, translation, timed, warm)
         out = session.drag(spec.part, translation(args.drags - 1), with_inputs=True)
         inputs = out["surface_samples_inputs"]
         dd = {"surface_samples_inputs": inputs, "verts_src": verts,
@@ -1428,6 +1501,7 @@ def main_ragged(args, vertex_counts, surface_counts):
             "checksum": _checksum(packed(out["verts_tgt_pred"]))}
     if args.normals:
         line.update(_normals_fields(ms_drag, ms_normals, sum(int(f.shape[0]) for _, f in spheres)))
+    line.update(selfint_fields)
     print(json.dumps(line), flush=True)
     session.close()
     return 0
@@ -1525,6 +1599,8 @@ def main(argv=None):
     if names is not None:
         if args.normals:
             sys.exit("nsdp_amd.edit: --normals times drags by rule (--part), not --handles")
+        if args.self_intersections:
+            sys.exit("nsdp_amd.edit: --self-intersections times drags by rule (--part), not --handles")
         if vertex_counts is not None:
             sys.exit("nsdp_amd.edit: --handles goes with --vertices / --batch, not with --vertex-counts")
         if args.vertices < 1 or (args.surface is not None and args.surface < 1) or args.drags < 1:
@@ -1536,7 +1612,7 @@ def main(argv=None):
         return main_ragged(args, vertex_counts, surface_counts)
     if args.vertices < 1 or (args.surface is not None and args.surface < 1) or args.drags < 1:
         sys.exit("nsdp_amd.edit: --vertices, --surface and --drags want positive integers")
-    sphere = sphere_for(args.vertices) if args.normals else None
+    sphere = sphere_for(args.vertices) if args.normals or args.self_intersections else None
     if sphere is not None:
         args.vertices = int(sphere[0].shape[0])
     device, config, spec, model, test_fn, timed, translation = _setup(args, args.surface or args.vertices)
@@ -1563,6 +1639,7 @@ def main(argv=None):
             session.drag(spec.part, translation(i))
         ms_drag = timed(lambda i: out.update(session.drag(spec.part, translation(i), clone=False)), args.drags)
         ms_normals = _timed_with_normals(args, session, spec, translation, timed, max(args.warmup, 1))
+        selfint_fields = _timed_with_self_intersections(args, session, spec, translation, timed, max(args.warmup, 1))
         out = session.drag(spec.part, translation(args.drags - 1), with_inputs=True)
         dd = {"surface_samples_inputs": out["surface_samples_inputs"], "verts_src": verts,
               "surface_samples_src": out["surface_samples_inputs"][:, :, 0:3].contiguous()}
@@ -1586,6 +1663,7 @@ def main(argv=None):
             "checksum": _checksum(out["verts_tgt_pred"])}
     if args.normals:
         line.update(_normals_fields(ms_drag, ms_normals, int(sphere[1].shape[0])))
+    line.update(selfint_fields)
     print(json.dumps(line), flush=True)
     session.close()
     return 0

@@ -36,6 +36,13 @@ Vertex normals, opt-in (nsdp_amd/mesh_normals.py; with neither key the files are
   test.vertex_normal_consistency: true    adds ``vnc`` to every pair: the mean over the vertices of |n_pred . n_gt|
                                           (``vertex_normal_consistency``), in the .txt, the .json and the batch's one ``.tolist()``.
 
+Self-intersections, opt-in (nsdp_amd/self_intersect.py; without the key the files are byte for byte what they were):
+  test.self_intersections: true           adds to every pair ``si``, the intersecting face pairs of the predicted mesh, ``si_faces``,
+                                          the share of its faces with a hit, and ``si_gt``, the pairs of the TARGET mesh -- which
+                                          tells a defect of the data from one of the model -- in the .txt, the .json and the batch's
+                                          one ``.tolist()``.  Their means are plain means (the <= 1.0 filter is the metrics').  Faces
+                                          the work guard skipped are named in a WARNING line.
+
 Refused by name: ``test.generate_pointcloud`` (point-cloud export).  Out of scope: ``--gpus N``, graph replay of the whole step.
 """
 from __future__ import annotations
@@ -145,6 +152,21 @@ def vertex_normal_consistency(n_pred, n_gt, offsets):
     return (m + segment_mean(hi, offsets).double()) + segment_mean(lo, offsets).double()
 
 
+SI_KEYS = ("si", "si_faces", "si_gt")
+
+
+def batch_self_intersections(faces, pred, target):
+    """{si, si_faces, si_gt, si_skipped} as [B] float64 of a batch: the predicted and the target vertex sets (RaggedPoints over
+    one layout) as two poses of the packed topology ``faces``, one call (the plan's Morton order is the prediction's).  The
+    store has clamped every face index into its mesh, so nothing is read back to validate them."""
+    from .self_intersect import SelfIntersectionPlan, self_intersections
+    plan = SelfIntersectionPlan(faces, pred.like(pred.packed.detach()), validate=False)
+    r = self_intersections(torch.stack([pred.packed.detach(), target.packed.detach()]), plan)
+    count = (faces.offsets[1:] - faces.offsets[:-1]).clamp(min=1).double()
+    return {"si": r.pairs[0].double(), "si_faces": r.faces_hit[0].double() / count, "si_gt": r.pairs[1].double(),
+            "si_skipped": r.skipped.sum(dim=0).double()}
+
+
 def export_meshes(directory, pair_infos, ext, verts, handle, faces, vert_counts, face_counts, normals=None):
     """Write the meshes of a batch that is already on the host.  ``verts``: part -> [cap, 3] fp32 for "source", "deformed",
     "target" and, where it is exported, "canonical"; ``handle`` [cap] bool; ``faces`` [fcap, 3] int32, local indices;
@@ -190,7 +212,9 @@ def evaluate(model, test_fn, store, config, experiment_directory, batch, seed, l
     mesh_dir = os.path.join(experiment_directory, split, test.get("mesh_folder", "meshes")) if test.get("generate_mesh") else None
     ext = test.get("mesh_format", "ply")
     with_normals, with_vnc = bool(test.get("export_normals")) and mesh_dir is not None, bool(test.get("vertex_normal_consistency"))
+    with_si = bool(test.get("self_intersections"))
     metrics = METRICS + (("vnc",) if with_vnc else ())
+    read = metrics + ((SI_KEYS + ("si_skipped",)) if with_si else ())      # (what the batch's one read-back carries)
     rows = []
     with open(os.path.join(experiment_directory, split + ".txt"), "w") as txt:
         def say(line):
@@ -205,16 +229,27 @@ def evaluate(model, test_fn, store, config, experiment_directory, batch, seed, l
                 n_pred, n_tgt, n_src = batch_normals(faces, [pred, out["verts_tgt"], out["verts_src"]])
             if with_vnc:
                 m["vnc"] = vertex_normal_consistency(n_pred, n_tgt, pred.offsets)
-                values = torch.stack([m[k].double() for k in metrics]).tolist()      # (fp32 -> double is exact: the same numbers)
+            if with_si:
+                m.update(batch_self_intersections(faces, pred, out["verts_tgt"]))
+            if with_vnc or with_si:
+                values = torch.stack([m[k].double() for k in read]).tolist()      # (fp32 -> double is exact: the same numbers)
             else:
                 values = torch.stack([m[k] for k in METRICS]).tolist()      # the batch's ONE read-back of metrics
             infos = [store.pairs[i] for i in out["index"]]
             for b, info in enumerate(infos):
                 row = {"index": int(out["index"][b]), "pair_info": list(info), "loss": float(loss)}
                 row.update({k: values[c][b] for c, k in enumerate(metrics)})
+                tail = ""
+                if with_si:
+                    at = len(metrics)
+                    row.update({"si": int(values[at][b]), "si_faces": values[at + 1][b], "si_gt": int(values[at + 2][b])})
+                    tail = "  si {:d}  si_faces {:.6e}  si_gt {:d}".format(row["si"], row["si_faces"], row["si_gt"])
+                    if values[at + 3][b]:
+                        say("WARNING: pair {:5d}: the work guard skipped {:d} faces of the predicted or the target mesh; their "
+                            "intersections are not counted".format(row["index"], int(values[at + 3][b])))
                 rows.append(row)
                 say("pair {:5d} {}_{} -> {}_{}  loss {:.6e}  ".format(row["index"], info[4], info[5], info[6], info[7], row["loss"])
-                    + "  ".join("{} {:.6e}".format(k, row[k]) for k in metrics))
+                    + "  ".join("{} {:.6e}".format(k, row[k]) for k in metrics) + tail)
             if mesh_dir is not None:
                 extra = [n_src, n_pred, n_tgt] if with_normals else []      # (in the same copy)
                 sets, handle, f = _to_host([out["verts_src"].packed, out["verts_cano"].packed, pred.packed.detach(),
@@ -224,6 +259,9 @@ def evaluate(model, test_fn, store, config, experiment_directory, batch, seed, l
         means, left_out = filtered_means(rows, metrics)
         say("mean over {} pairs (values <= 1.0 only)  ".format(len(rows)) + "  ".join("{} {:.6e}".format(k, means[k]) for k in metrics)
             + "  left out: " + ", ".join("{} {}".format(k, left_out[k]) for k in metrics))
+        if with_si:
+            means.update({k: float(np.mean([r[k] for r in rows])) if rows else float("nan") for k in SI_KEYS})
+            say("mean over {} pairs (every value)  ".format(len(rows)) + "  ".join("{} {:.6e}".format(k, means[k]) for k in SI_KEYS))
     with open(os.path.join(experiment_directory, split + ".json"), "w") as f:
         json.dump({"pairs": rows, "means": means, "left_out": left_out}, f, indent=1)
     return rows
