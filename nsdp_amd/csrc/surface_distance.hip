@@ -1,6 +1,7 @@
 // Exact point-to-mesh distance (include/nsdp_surface.h): for every query the closest point of a triangle mesh.
 //
-//   boxes_kernel    one wave per block of 64 consecutive faces of a mesh: the bounding box of the block's corners -> workspace
+//   boxes_kernel    (mesh_blocks.h, shared with ray_cast.hip) one wave per block of 64 consecutive faces of a mesh: the bounding
+//                   box of the block's corners -> workspace
 //   init_kernel     one lane per query: its start key -- (FLT_MAX, no face), or with the bound pass the smallest over its mesh's blocks
 //                   of the largest squared distance to a box, raised by the margin and one ulp (some whole face lies in each box)
 //   scan_kernel     one wave per 64 queries of a mesh and per part of the mesh's blocks: a wave-wide vote on box distance
@@ -14,23 +15,17 @@
 
 #include "../../include/nsdp_surface.h"
 #include "common.h"
+#include "mesh_blocks.h"
 #include "prof.h"
 #include "ragged.h"
 
 namespace {
 
-constexpr int kWave = 64;                       // a workgroup is one wave: 64 queries, and a block is 64 faces
-constexpr int kBlock = 64;
 constexpr int kRec = 9;                         // a staged face: 9 dwords (a, b, c) -- an odd stride, see scan_kernel
-constexpr int kMaxRows = 1 << 20;               // rows of one kind a shape may hold
 constexpr float kMargin = 1.9073486328125e-06f; // 2^-19 = 32 * 2^-24: 17 (the envelope) + 5 (a box distance) + 2 (the margin's own
                                                 // product and subtraction), the rest slack for second order -- DESIGN.md 4k
 constexpr unsigned long long kNoFace = 0xFFFFFFFFull;
 constexpr unsigned long long kStartKey = (0x7F7FFFFFull << 32) | kNoFace;      // (FLT_MAX bits, no face)
-
-struct V3 {
-  float x, y, z;
-};
 
 __device__ __forceinline__ V3 sub(const V3 &a, const V3 &b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
 __device__ __forceinline__ float dot(const V3 &a, const V3 &b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
@@ -83,58 +78,6 @@ __device__ __forceinline__ void box_dist(const V3 &p, const float *__restrict__ 
   const V3 f = {fmaxf(-ax, -bx), fmaxf(-ay, -by), fmaxf(-az, -bz)};
   lo2 = dot(n, n);
   hi2 = dot(f, f);
-}
-
-// A shape's rows of the three packed sets, clamped as ragged.h clamps them; a mesh without vertices has no faces.
-struct Mesh {
-  int vlo, vn, flo, fhi, slot0;      // slot0: the workspace slot of the mesh's first block -- flo / 64 + b: the blocks of shape s end
-                                     // at or before (its last face row) / 64 + s + 1, where those of shape s + 1 begin at the earliest
-};
-
-__device__ __forceinline__ Mesh mesh_of(const int32_t *__restrict__ vert_offsets, const int32_t *__restrict__ face_offsets, int b,
-                                        int vcap, int fcap) {
-  Mesh m;
-  int vhi;
-  nsdp::ragged_range(vert_offsets, b, vcap, m.vlo, vhi);
-  nsdp::ragged_range(face_offsets, b, fcap, m.flo, m.fhi);
-  m.vn = vhi - m.vlo;
-  if (m.vn <= 0) m.fhi = m.flo;
-  m.slot0 = m.flo / kBlock + b;
-  return m;
-}
-
-__device__ __forceinline__ V3 corner(const float *__restrict__ verts, const Mesh &m, int local) {
-  const size_t r = static_cast<size_t>(m.vlo + min(max(local, 0), m.vn - 1)) * 3;
-  return {verts[r], verts[r + 1], verts[r + 2]};
-}
-
-__device__ __forceinline__ float wave_min(float v) {
-  for (int s = 32; s > 0; s >>= 1) v = fminf(v, __shfl_xor(v, s, kWave));
-  return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-  for (int s = 32; s > 0; s >>= 1) v = fmaxf(v, __shfl_xor(v, s, kWave));
-  return v;
-}
-
-__global__ __launch_bounds__(kWave) void boxes_kernel(const float *__restrict__ verts, const int32_t *__restrict__ vert_offsets,
-                                                      const int32_t *__restrict__ faces, const int32_t *__restrict__ face_offsets,
-                                                      int B, int vcap, int fcap, float *__restrict__ boxes) {
-  int b, row0, end;
-  if (!nsdp::ragged_tile<kBlock>(face_offsets, B, fcap, static_cast<int>(blockIdx.x), b, row0, end)) return;
-  const Mesh m = mesh_of(vert_offsets, face_offsets, b, vcap, fcap);
-  if (m.fhi <= m.flo) return;                                  // (faces over no vertices: the mesh has no blocks)
-  const int f = min(row0 + static_cast<int>(threadIdx.x), end - 1);      // (a partial block: the surplus lanes repeat its last face)
-  const size_t fr = static_cast<size_t>(f) * 3;
-  const V3 a = corner(verts, m, faces[fr]), c1 = corner(verts, m, faces[fr + 1]), c2 = corner(verts, m, faces[fr + 2]);
-  const float lx = wave_min(fminf(fminf(a.x, c1.x), c2.x)), ly = wave_min(fminf(fminf(a.y, c1.y), c2.y)),
-              lz = wave_min(fminf(fminf(a.z, c1.z), c2.z));
-  const float hx = wave_max(fmaxf(fmaxf(a.x, c1.x), c2.x)), hy = wave_max(fmaxf(fmaxf(a.y, c1.y), c2.y)),
-              hz = wave_max(fmaxf(fmaxf(a.z, c1.z), c2.z));
-  if (threadIdx.x == 0) {
-    float *box = boxes + static_cast<size_t>(m.slot0 + (row0 - m.flo) / kBlock) * 6;
-    box[0] = lx, box[1] = ly, box[2] = lz, box[3] = hx, box[4] = hy, box[5] = hz;
-  }
 }
 
 __global__ __launch_bounds__(kWave) void init_kernel(const float *__restrict__ query, const int32_t *__restrict__ query_offsets,
@@ -248,8 +191,6 @@ bool sizes_ok(int B, int qcap, int fcap) {
   return B >= 1 && B <= 65535 && qcap >= 1 && fcap >= 1 && qcap <= static_cast<long long>(kMaxRows) * B &&
          fcap <= static_cast<long long>(kMaxRows) * B;
 }
-
-long long box_slots(int B, int fcap) { return static_cast<long long>(fcap) / kBlock + B + 1; }
 
 }  // namespace
 

@@ -374,7 +374,7 @@ class _Session:
     def _open_normals(self):
         """The last step of ``_open`` (outside any capture): the topology of ``faces`` over the vertices' layout -- the corner
         lists, one host read -- and the source mesh's normals.  Without faces the session holds neither."""
-        self.topology = self.verts_src_normals = self.selfint_plan = None
+        self.topology = self.verts_src_normals = self.selfint_plan = self.pick_plan = None
         if self.faces is not None:
             from .mesh_normals import MeshTopology, vertex_normals
             self.topology = MeshTopology(self.faces, self.verts)
@@ -396,6 +396,40 @@ class _Session:
             from .self_intersect import SelfIntersectionPlan
             self.selfint_plan = SelfIntersectionPlan(self.faces, self.verts, topology=self.topology)
         return bool(wanted)
+
+    def pick(self, origins, directions, verts=None):
+        """A click as a ray (nsdp_amd/ray_cast.py, include/nsdp_raycast.h): the first face of mesh ``b`` that the rays ``origins
+        + t directions`` of shape ``b`` meet ([B, n, 3] fp32 on the GPU; RaggedPoints over the batch for a packed session) --
+        against the source mesh, or against ``verts``, a vertex set of the same topology such as a drag's ``verts_tgt_pred``.
+        Returns ``t`` (FLT_MAX without a hit), ``face`` (local to its mesh, -1: none), ``bary`` (the weights of the face's
+        corners), ``vertex`` (the hit face's corner of the largest weight, the lowest corner on ties; local, -1: none) and
+        ``label``: the vertex's handle label of ``set_handles`` -- the ``vert_labels``, or the labels themselves where the cloud
+        is the vertex set -- 0 without a hit, None before any labels are set.  A call of its own: it is no part of a drag's
+        graph and the predictions keep their bits.  The plan (the faces in Morton order of the source mesh) is made at the
+        first pick."""
+        import torch
+        from .ragged import RaggedPoints, shape_ids
+        if self.topology is None:
+            raise ValueError(self._refused + "pick() without faces: the session was opened without `faces`, and a ray meets the "
+                             "mesh's triangles -- open it with faces=...")
+        from .ray_cast import RayCastPlan, cast_rays, hit_vertices
+        if self.pick_plan is None:
+            self.pick_plan = RayCastPlan(self.faces, self.verts, topology=self.topology)
+        with torch.no_grad():
+            hits = cast_rays(origins, directions, self.verts if verts is None else verts, self.pick_plan, return_bary=True, count=False)
+            vertex = hit_vertices(hits, self.pick_plan)
+            labels = self._vlabels if self._vert_labelled else (self._labels if self.same else None)
+            label = None
+            if labels is not None:
+                if isinstance(vertex, RaggedPoints):
+                    topo, v = self.topology, vertex.packed[:, 0]
+                    owner = shape_ids(origins.offsets, origins.capacity).clamp(max=topo.shapes - 1)
+                    rows = (v.long().clamp(min=0) + topo.vert_offsets[:-1].long()[owner]).clamp(0, topo.vcap - 1)
+                    label = vertex.like(torch.where(v >= 0, labels.reshape(-1)[rows], labels.new_zeros(())).unsqueeze(1))
+                else:
+                    got = torch.gather(labels, 1, vertex.long().clamp(min=0))
+                    label = torch.where(vertex >= 0, got, torch.zeros_like(got))
+        return {"t": hits.t, "face": hits.face, "bary": hits.bary, "vertex": vertex, "label": label}
 
     def _with_self_intersections(self, pred, lead=None):
         """``pred`` with the self-intersections of its vertices (nsdp_amd/self_intersect.py): the entry's launches behind the
@@ -675,7 +709,7 @@ class _Session:
     def close(self):
         self._drop_graphs()
         self._forget_handles()
-        for name in self._cached + ("topology", "verts_src_normals", "selfint_plan"):
+        for name in self._cached + ("topology", "verts_src_normals", "selfint_plan", "pick_plan"):
             setattr(self, name, None)
 
     def __enter__(self):
@@ -1289,6 +1323,9 @@ def build_parser():
     ap.add_argument("--self-intersections", action="store_true", dest="self_intersections",
                     help="drag the sphere mesh of --normals and print, per drag, the intersecting face pairs of every deformed "
                          "mesh (self_intersections=True), and the drag's time with them")
+    ap.add_argument("--pick", default=None, metavar="ox,oy,oz,dx,dy,dz",
+                    help="drag the sphere mesh of --normals and print what the ray from (ox, oy, oz) along (dx, dy, dz) picks -- t, "
+                         "face, barycentric weights, vertex -- on the source mesh and on the last drag's prediction (pick())")
     ap.add_argument("--weight_file", default=None, help="weights of the whole model (default: procedural weights)")
     ap.add_argument("--out", default=None, help="directory for the last drag's predictions (<key>.npy)")
     return ap
@@ -1413,6 +1450,40 @@ def _timed_with_self_intersections(args, session, spec, translation, timed, warm
         print(f"drag {i}: self-intersecting face pairs per mesh {pairs}, faces skipped by the guard {skipped}", flush=True)
     return {"self_intersections": True, "ms_per_drag_self_intersections": round(ms, 4),
             "self_intersection_pairs": [c[0] for c in counts], "self_intersection_skipped": [c[1] for c in counts]}
+
+
+def pick_from_args(args):
+    """--pick ox,oy,oz,dx,dy,dz -> the six numbers (None without the flag)."""
+    if args.pick is None:
+        return None
+    try:
+        ray = [float(x) for x in args.pick.split(",")]
+    except ValueError:
+        ray = []
+    if len(ray) != 6:
+        sys.exit(f"nsdp_amd.edit: --pick wants six numbers ox,oy,oz,dx,dy,dz, got {args.pick!r}")
+    return ray
+
+
+def _picked(ray, session, out, batch, device, timed, drags):
+    """--pick: the ray against the source mesh and against the last drag's prediction, printed -> the JSON fields (with the
+    time of one pick against the prediction: a call of its own beside the drag)."""
+    import torch
+    if ray is None:
+        return {}
+    o = torch.tensor(ray[:3], dtype=torch.float32, device=device).expand(batch, 1, 3).contiguous()
+    d = torch.tensor(ray[3:], dtype=torch.float32, device=device).expand(batch, 1, 3).contiguous()
+    fields = {"pick_ray": ray}
+    for name, verts in (("source", None), ("prediction", out["verts_tgt_pred"])):
+        r = session.pick(o, d, verts)
+        row = torch.cat([r["t"].double(), r["face"].double(), r["vertex"].double(), r["bary"][:, 0].double()], dim=1).tolist()
+        for b, (t, face, vertex, b0, b1, b2) in enumerate(row):
+            hit = f"t {t:.6g}  face {int(face)}  bary ({b0:.4f}, {b1:.4f}, {b2:.4f})  vertex {int(vertex)}" if face >= 0 else "no hit"
+            print(f"pick on the {name} mesh, shape {b}: {hit}", flush=True)
+        fields["pick_" + name] = [{"t": t if face >= 0 else None, "face": int(face), "vertex": int(vertex), "bary": [b0, b1, b2]}
+                                  for t, face, vertex, b0, b1, b2 in row]
+    fields["ms_per_pick"] = round(timed(lambda i: session.pick(o, d, out["verts_tgt_pred"]), drags), 4)
+    return fields
 
 
 def _normals_fields(ms_drag, ms_normals, faces):
@@ -1601,6 +1672,8 @@ def main(argv=None):
             sys.exit("nsdp_amd.edit: --normals times drags by rule (--part), not --handles")
         if args.self_intersections:
             sys.exit("nsdp_amd.edit: --self-intersections times drags by rule (--part), not --handles")
+        if args.pick is not None:
+            sys.exit("nsdp_amd.edit: --pick goes with drags by rule (--part), not --handles")
         if vertex_counts is not None:
             sys.exit("nsdp_amd.edit: --handles goes with --vertices / --batch, not with --vertex-counts")
         if args.vertices < 1 or (args.surface is not None and args.surface < 1) or args.drags < 1:
@@ -1609,10 +1682,13 @@ def main(argv=None):
     if vertex_counts is not None:
         if (args.surface is not None and args.surface < 1) or args.drags < 1:
             sys.exit("nsdp_amd.edit: --surface and --drags want positive integers")
+        if args.pick is not None:
+            sys.exit("nsdp_amd.edit: --pick goes with --vertices / --batch, not with --vertex-counts")
         return main_ragged(args, vertex_counts, surface_counts)
+    ray = pick_from_args(args)
     if args.vertices < 1 or (args.surface is not None and args.surface < 1) or args.drags < 1:
         sys.exit("nsdp_amd.edit: --vertices, --surface and --drags want positive integers")
-    sphere = sphere_for(args.vertices) if args.normals or args.self_intersections else None
+    sphere = sphere_for(args.vertices) if args.normals or args.self_intersections or ray is not None else None
     if sphere is not None:
         args.vertices = int(sphere[0].shape[0])
     device, config, spec, model, test_fn, timed, translation = _setup(args, args.surface or args.vertices)
@@ -1641,6 +1717,7 @@ def main(argv=None):
         ms_normals = _timed_with_normals(args, session, spec, translation, timed, max(args.warmup, 1))
         selfint_fields = _timed_with_self_intersections(args, session, spec, translation, timed, max(args.warmup, 1))
         out = session.drag(spec.part, translation(args.drags - 1), with_inputs=True)
+        pick_fields = _picked(ray, session, out, batch, device, timed, args.drags)
         dd = {"surface_samples_inputs": out["surface_samples_inputs"], "verts_src": verts,
               "surface_samples_src": out["surface_samples_inputs"][:, :, 0:3].contiguous()}
         for _ in range(max(args.warmup, 1)):
@@ -1664,6 +1741,7 @@ def main(argv=None):
     if args.normals:
         line.update(_normals_fields(ms_drag, ms_normals, int(sphere[1].shape[0])))
     line.update(selfint_fields)
+    line.update(pick_fields)
     print(json.dumps(line), flush=True)
     session.close()
     return 0

@@ -43,6 +43,14 @@ Self-intersections, opt-in (nsdp_amd/self_intersect.py; without the key the file
                                           one ``.tolist()``.  Their means are plain means (the <= 1.0 filter is the metrics').  Faces
                                           the work guard skipped are named in a WARNING line.
 
+Volume IoU, opt-in (nsdp_amd/ray_cast.py; without the key the files are byte for byte what they were):
+  test.volume_iou: N                      adds ``iou`` to every pair: the volume IoU of the predicted against the target mesh from N
+                                          uniform samples in the pair's joint bounding box (``ray_cast.volume_iou``; the draws are
+                                          seeded by (seed, step): ``iou_generator``), in the .txt, the .json and the batch's one
+                                          ``.tolist()``, with a plain mean.  Inside is the parity of ray crossings: it means
+                                          something on closed meshes only, so a batch with open edges gets a WARNING line that
+                                          names its pairs.
+
 Refused by name: ``test.generate_pointcloud`` (point-cloud export).  Out of scope: ``--gpus N``, graph replay of the whole step.
 """
 from __future__ import annotations
@@ -167,6 +175,23 @@ def batch_self_intersections(faces, pred, target):
             "si_skipped": r.skipped.sum(dim=0).double()}
 
 
+def iou_generator(device, seed, step):
+    """The generator of batch ``step``'s volume-IoU samples: seeded by (seed, step), apart from ``metric_samples``' draws."""
+    return torch.Generator(device=device).manual_seed(((int(seed) * 1000003 + int(step)) * 2 + 1) & 0x7FFFFFFFFFFFFFFF)
+
+
+def batch_volume_iou(faces, pred, target, points, seed, step):
+    """{iou, iou_open} as [B] float64 of a batch: the volume IoU of the predicted against the target vertex sets (RaggedPoints
+    over one layout, two poses of the packed topology ``faces``) from ``points`` samples per pair, and every mesh's open edges.
+    The store has clamped every face index into its mesh, so nothing is read back to validate them -- nor for the open edges,
+    which stay on the device."""
+    from .ray_cast import RayCastPlan, volume_iou
+    verts = pred.like(pred.packed.detach())
+    plan = RayCastPlan(faces, verts, validate=False)
+    iou = volume_iou(verts, target.like(target.packed.detach()), plan, int(points), iou_generator(verts.device, seed, step))[0]
+    return {"iou": iou, "iou_open": plan.open_edges_per_mesh.double()}
+
+
 def export_meshes(directory, pair_infos, ext, verts, handle, faces, vert_counts, face_counts, normals=None):
     """Write the meshes of a batch that is already on the host.  ``verts``: part -> [cap, 3] fp32 for "source", "deformed",
     "target" and, where it is exported, "canonical"; ``handle`` [cap] bool; ``faces`` [fcap, 3] int32, local indices;
@@ -213,8 +238,13 @@ def evaluate(model, test_fn, store, config, experiment_directory, batch, seed, l
     ext = test.get("mesh_format", "ply")
     with_normals, with_vnc = bool(test.get("export_normals")) and mesh_dir is not None, bool(test.get("vertex_normal_consistency"))
     with_si = bool(test.get("self_intersections"))
+    iou_points = test.get("volume_iou") or 0
+    if isinstance(iou_points, bool) or not isinstance(iou_points, int) or iou_points < 0:
+        raise EvaluateError(f"evaluate: test.volume_iou = {test.get('volume_iou')!r}: the samples per pair, a positive integer "
+                            "(not true / false)")
     metrics = METRICS + (("vnc",) if with_vnc else ())
-    read = metrics + ((SI_KEYS + ("si_skipped",)) if with_si else ())      # (what the batch's one read-back carries)
+    read = metrics + ((SI_KEYS + ("si_skipped",)) if with_si else ()) + (("iou", "iou_open") if iou_points else ())
+    # (read: what the batch's one read-back carries)
     rows = []
     with open(os.path.join(experiment_directory, split + ".txt"), "w") as txt:
         def say(line):
@@ -231,11 +261,20 @@ def evaluate(model, test_fn, store, config, experiment_directory, batch, seed, l
                 m["vnc"] = vertex_normal_consistency(n_pred, n_tgt, pred.offsets)
             if with_si:
                 m.update(batch_self_intersections(faces, pred, out["verts_tgt"]))
-            if with_vnc or with_si:
+            if iou_points:
+                m.update(batch_volume_iou(faces, pred, out["verts_tgt"], iou_points, seed, step))
+            if with_vnc or with_si or iou_points:
                 values = torch.stack([m[k].double() for k in read]).tolist()      # (fp32 -> double is exact: the same numbers)
             else:
                 values = torch.stack([m[k] for k in METRICS]).tolist()      # the batch's ONE read-back of metrics
             infos = [store.pairs[i] for i in out["index"]]
+            if iou_points:
+                at_iou = len(read) - 2
+                not_closed = [int(out["index"][b]) for b in range(len(infos)) if values[at_iou + 1][b]]
+                if not_closed:
+                    say("WARNING: pairs {}: the mesh has open edges ({}); inside is the parity of ray crossings and the iou of "
+                        "these pairs depends on where the holes are".format(not_closed, ", ".join(
+                            str(int(values[at_iou + 1][b])) for b in range(len(infos)) if values[at_iou + 1][b])))
             for b, info in enumerate(infos):
                 row = {"index": int(out["index"][b]), "pair_info": list(info), "loss": float(loss)}
                 row.update({k: values[c][b] for c, k in enumerate(metrics)})
@@ -247,6 +286,9 @@ def evaluate(model, test_fn, store, config, experiment_directory, batch, seed, l
                     if values[at + 3][b]:
                         say("WARNING: pair {:5d}: the work guard skipped {:d} faces of the predicted or the target mesh; their "
                             "intersections are not counted".format(row["index"], int(values[at + 3][b])))
+                if iou_points:
+                    row["iou"] = values[at_iou][b]
+                    tail += "  iou {:.6e}".format(row["iou"])
                 rows.append(row)
                 say("pair {:5d} {}_{} -> {}_{}  loss {:.6e}  ".format(row["index"], info[4], info[5], info[6], info[7], row["loss"])
                     + "  ".join("{} {:.6e}".format(k, row[k]) for k in metrics) + tail)
@@ -262,6 +304,9 @@ def evaluate(model, test_fn, store, config, experiment_directory, batch, seed, l
         if with_si:
             means.update({k: float(np.mean([r[k] for r in rows])) if rows else float("nan") for k in SI_KEYS})
             say("mean over {} pairs (every value)  ".format(len(rows)) + "  ".join("{} {:.6e}".format(k, means[k]) for k in SI_KEYS))
+        if iou_points:
+            means["iou"] = float(np.mean([r["iou"] for r in rows])) if rows else float("nan")
+            say("mean over {} pairs (every value)  iou {:.6e}".format(len(rows), means["iou"]))
     with open(os.path.join(experiment_directory, split + ".json"), "w") as f:
         json.dump({"pairs": rows, "means": means, "left_out": left_out}, f, indent=1)
     return rows
