@@ -23,7 +23,7 @@
 #include "../../include/nsdp_scatter.h"
 #include "common.h"
 #include "list_reduce.h"
-#include "packed_rows.h"      // a row's owner
+#include "mesh_corners.h"     // struct Mesh, a corner's row
 #include "prof.h"
 
 #pragma clang fp contract(off)
@@ -37,24 +37,6 @@ constexpr int kMaxPoses = 65535;          // (a grid's y extent)
 
 inline size_t align16(size_t v) { return (v + 15) & ~static_cast<size_t>(15); }
 inline bool aligned_to(const void *p, size_t to) { return reinterpret_cast<uintptr_t>(p) % to == 0; }
-
-struct Mesh {
-  const int32_t *faces, *face_offsets, *vert_offsets;
-  int B, vcap, fcap;
-};
-
-// the packed vertex rows the corners of face row q < fcap name; false: a dead face (rows untouched)
-__device__ __forceinline__ bool corner_rows(const Mesh &m, long long q, int rows[3]) {
-  int b;
-  if (!owner_of_lane(m.face_offsets, m.B, m.fcap, q, b)) return false;
-  int first, end;
-  shape_range(m.vert_offsets, b, m.vcap, first, end);
-  const int hi = max(end - first - 1, 0);
-  const int32_t *f = m.faces + static_cast<size_t>(q) * 3;
-#pragma unroll
-  for (int j = 0; j < 3; ++j) rows[j] = min(first + clamped(f[j], 0, hi), m.vcap - 1);
-  return true;
-}
 
 __global__ __launch_bounds__(kThreads) void mesh_corner_rows_kernel(const Mesh m, int32_t *__restrict__ table) {
   const long long q = static_cast<long long>(blockIdx.x) * kThreads + threadIdx.x;

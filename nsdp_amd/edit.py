@@ -374,7 +374,7 @@ class _Session:
     def _open_normals(self):
         """The last step of ``_open`` (outside any capture): the topology of ``faces`` over the vertices' layout -- the corner
         lists, one host read -- and the source mesh's normals.  Without faces the session holds neither."""
-        self.topology = self.verts_src_normals = self.selfint_plan = self.pick_plan = None
+        self.topology = self.verts_src_normals = self.selfint_plan = self.pick_plan = self.brush_plan = None
         if self.faces is not None:
             from .mesh_normals import MeshTopology, vertex_normals
             self.topology = MeshTopology(self.faces, self.verts)
@@ -700,6 +700,89 @@ class _Session:
                 labels = torch.where(move != 0, torch.full_like(labels, i + 1), labels)
         return labels, count
 
+    def labels_from_brush(self, strokes, verts=False, pose_verts=None):
+        """Labels for ``set_handles`` from brush strokes on the mesh (nsdp_amd/geodesic.py, include/nsdp_geodesic.h):
+        ``strokes`` is a list of ``(vertex, radius)`` -- ``vertex`` what ``pick()`` returns as ``"vertex"``, or any [B] / [B, s]
+        integer tensor of local vertex indices (-1: none, the stroke labels nothing in that shape), ``radius`` a float or a [B]
+        tensor -- and stroke i labels every vertex within ``radius`` of its seeds ALONG the mesh's edges with i + 1 (closed at
+        the radius; earlier strokes win where they overlap); ``count = len(strokes)``.  Distances are measured on the source
+        mesh, or on ``pose_verts``, a vertex set of the same topology such as a drag's ``verts_tgt_pred``.  Returns ``(labels,
+        count)`` as ``labels_from_parts`` does: over the cloud -- where the cloud is separate the vertex labels are carried to
+        it through ``closest_on_mesh`` + ``transfer_vertex_labels`` on the source mesh, and ``verts=True`` gives the vertex
+        labels themselves.  Set-up work, no part of a drag's graph: the predictions keep their bits.  The plan (the vertices in
+        Morton order of the source mesh) is made at the first brush."""
+        import torch
+        from .ragged import RaggedPoints, shape_ids
+        if self.topology is None:
+            raise ValueError(self._refused + "labels_from_brush() without faces: the session was opened without `faces`, and a "
+                             "brush measures along the mesh's triangles -- open it with faces=...")
+        strokes = list(strokes)
+        if not 1 <= len(strokes) <= 255 or any(not isinstance(s, (tuple, list)) or len(s) != 2 for s in strokes):
+            raise ValueError(f"labels_from_brush: 1..255 strokes (vertex, radius), got {len(strokes)}")
+        from .geodesic import GeodesicPlan, geodesic_distances
+        B, on, cloud_rows, vert_rows = self._layout()
+        topo = self.topology
+        with torch.no_grad():
+            if self.brush_plan is None:
+                self.brush_plan = GeodesicPlan(self.faces, self.verts, topology=topo)
+            mesh = self.verts if pose_verts is None else pose_verts
+            ragged = isinstance(self.verts, RaggedPoints)
+            labels = torch.zeros(vert_rows, dtype=torch.uint8, device=on.device)
+            self.brush_stats = []
+            for i in reversed(range(len(strokes))):
+                vertex, radius = strokes[i]
+                if isinstance(vertex, RaggedPoints):
+                    vertex = vertex.padded(-1)
+                if not torch.is_tensor(vertex) or vertex.is_floating_point() or vertex.dim() < 1 or vertex.shape[0] != B:
+                    raise ValueError(f"labels_from_brush: stroke {i}: vertex must be an integer tensor [B] or [B, s] over the {B} "
+                                     "shapes (pick()'s \"vertex\")")
+                seeds = vertex.to(on.device).reshape(B, -1)
+                if torch.is_tensor(radius):
+                    if radius.numel() != B:
+                        raise ValueError(f"labels_from_brush: stroke {i}: radius must be a float or [B] = [{B}]")
+                    per_shape = radius.to(on.device, torch.float32).reshape(B)
+                    limit = float(per_shape.max())      # (set-up work: one read; a path within r_b has every prefix within it)
+                else:
+                    per_shape, limit = None, float(radius)
+                if not limit >= 0.0:
+                    raise ValueError(f"labels_from_brush: stroke {i}: radius {limit} is NaN or negative")
+                dist, stats = geodesic_distances(mesh, self.brush_plan, seeds, limit=limit, return_stats=True)
+                self.brush_stats.insert(0, stats)      # (per stroke, in the strokes' order: rounds and calls)
+                dist = dist.packed[:, 0] if ragged else dist.reshape(vert_rows)
+                if per_shape is None:
+                    inside = dist <= limit
+                elif ragged:
+                    inside = dist <= per_shape[shape_ids(topo.vert_offsets, topo.vcap).clamp(max=B - 1)]
+                else:
+                    inside = dist <= per_shape[:, None]
+                labels = torch.where(inside, torch.full_like(labels, i + 1), labels)
+            if self.same or verts:
+                return labels, len(strokes)
+            return self._labels_to_cloud(labels, cloud_rows), len(strokes)
+
+    def _labels_to_cloud(self, vert_labels, cloud_rows):
+        """Vertex labels carried to a separate cloud: every cloud point takes the label of the closest mesh point's corner of
+        the largest weight (``closest_on_mesh`` on the source mesh, ``transfer_vertex_labels``' rule)."""
+        import torch
+        from .ragged import RaggedPoints, shape_ids
+        from .surface_distance import closest_on_mesh, transfer_vertex_labels
+        if not isinstance(self.verts, RaggedPoints):
+            B = self.verts.shape[0]
+            faces = self.faces if self.faces.dim() == 3 else self.faces[None].expand(B, -1, -1)
+            _, face, bary = closest_on_mesh(self.surface, self.verts, faces.contiguous())
+            return transfer_vertex_labels(vert_labels, faces, face, bary).reshape(cloud_rows)
+        cloud = RaggedPoints.from_list(list(self.surface)) if self.rect else self.surface
+        _, face, bary = closest_on_mesh(cloud, self.verts, self.faces)
+        topo, B = self.topology, self.verts.batch
+        owner = shape_ids(cloud.offsets, cloud.capacity).clamp(max=B - 1)
+        f = face.packed[:, 0]
+        rows = (f.long().clamp(min=0) + topo.face_offsets.long()[owner]).clamp(0, topo.fcap - 1)
+        corner = torch.argmax(bary.packed, dim=1, keepdim=True)
+        local = torch.gather(topo.faces.long()[rows], 1, corner)[:, 0]
+        vrow = (local + topo.vert_offsets.long()[owner]).clamp(0, topo.vcap - 1)
+        out = torch.where(f >= 0, vert_labels[vrow], torch.zeros_like(vert_labels[vrow]))
+        return out.reshape(cloud_rows)
+
     # ------------------------------------------------------------------ the end
     def _drop_graphs(self):
         for step in self._steps.values():
@@ -709,7 +792,7 @@ class _Session:
     def close(self):
         self._drop_graphs()
         self._forget_handles()
-        for name in self._cached + ("topology", "verts_src_normals", "selfint_plan", "pick_plan"):
+        for name in self._cached + ("topology", "verts_src_normals", "selfint_plan", "pick_plan", "brush_plan"):
             setattr(self, name, None)
 
     def __enter__(self):
@@ -1326,6 +1409,10 @@ def build_parser():
     ap.add_argument("--pick", default=None, metavar="ox,oy,oz,dx,dy,dz",
                     help="drag the sphere mesh of --normals and print what the ray from (ox, oy, oz) along (dx, dy, dz) picks -- t, "
                          "face, barycentric weights, vertex -- on the source mesh and on the last drag's prediction (pick())")
+    ap.add_argument("--brush", action="append", default=None, metavar="ox,oy,oz,dx,dy,dz,radius",
+                    help="(repeatable) on the sphere mesh of --normals: pick the vertex the ray from (ox, oy, oz) along (dx, dy, dz) "
+                         "meets and brush a handle of that geodesic radius around it (labels_from_brush); the handles are set and "
+                         "posed -- the first by --rotate-deg about its centroid plus --translate, the others pinned")
     ap.add_argument("--weight_file", default=None, help="weights of the whole model (default: procedural weights)")
     ap.add_argument("--out", default=None, help="directory for the last drag's predictions (<key>.npy)")
     return ap
@@ -1486,6 +1573,69 @@ def _picked(ray, session, out, batch, device, timed, drags):
     return fields
 
 
+def brushes_from_args(args):
+    """--brush ox,oy,oz,dx,dy,dz,radius (repeatable) -> a list of seven numbers per brush (None without the flag)."""
+    if not args.brush:
+        return None
+    out = []
+    for text in args.brush:
+        try:
+            row = [float(x) for x in text.split(",")]
+        except ValueError:
+            row = []
+        if len(row) != 7 or not row[6] >= 0.0:
+            sys.exit(f"nsdp_amd.edit: --brush wants seven numbers ox,oy,oz,dx,dy,dz,radius with radius >= 0, got {text!r}")
+        out.append(row)
+    if len(out) > 255:
+        sys.exit("nsdp_amd.edit: at most 255 --brush handles (the labels are bytes)")
+    return out
+
+
+def _brushed(brushes, session, args, spec, batch, device, timed):
+    """--brush: every ray picked on the source mesh, a handle brushed around each picked vertex, the handles set and posed
+    -- the size of each handle, the rounds and the milliseconds printed -> the JSON fields."""
+    import numpy as np
+    import torch
+    if brushes is None:
+        return {}
+    strokes = []
+    for row in brushes:
+        o = torch.tensor(row[:3], dtype=torch.float32, device=device).expand(batch, 1, 3).contiguous()
+        d = torch.tensor(row[3:6], dtype=torch.float32, device=device).expand(batch, 1, 3).contiguous()
+        strokes.append((session.pick(o, d)["vertex"], row[6]))
+    session.labels_from_brush(strokes)      # (the first brush makes the plan)
+    box = {}
+    ms_brush = timed(lambda i: box.update(r=session.labels_from_brush(strokes)), args.drags)
+    labels, count = box["r"]
+    stats = list(session.brush_stats)
+    vlabels = None if session.same else session.labels_from_brush(strokes, verts=True)[0]
+    session.set_handles(labels, count, vlabels)
+    own = labels if vlabels is None else vlabels
+    sizes = torch.stack([(own == h + 1).sum(dim=1) for h in range(count)], dim=1)                        # [B, count]
+    first = (own == 1)[:, :, None].double()
+    pivots = (session.verts.double() * first).sum(dim=1) / first.sum(dim=1).clamp(min=1.0)
+    seeds = torch.stack([s[0].reshape(batch, -1)[:, 0] for s in strokes], dim=1)
+    sizes, pivots, seeds = sizes.tolist(), pivots.cpu().numpy(), seeds.tolist()                            # (set-up reads)
+    try:
+        axis = tuple(float(v) for v in args.axis.split(","))
+    except ValueError:
+        axis = ()
+    if len(axis) != 3 or not any(axis):
+        sys.exit(f"nsdp_amd.edit: --axis wants a non-zero ax,ay,az, got {args.axis!r}")
+    motions = [[Motion.rotate(axis, args.rotate_deg, pivot=pivots[b]).then(Motion.translate(np.asarray(spec.translation, np.float64)))]
+               + [Motion.identity()] * (count - 1) for b in range(batch)]
+    for _ in range(max(args.warmup, 1)):
+        session.pose(motions)
+    ms_pose = timed(lambda i: session.pose(motions, clone=False), args.drags)
+    for b in range(batch):
+        for h in range(count):
+            print(f"brush {h} on shape {b}: vertex {seeds[b][h]}, radius {brushes[h][6]:g}: {sizes[b][h]} points, "
+                  f"{stats[h]['rounds']} rounds in {stats[h]['calls']} calls", flush=True)
+    print(f"{count} brush(es): {ms_brush:.3f} ms; a pose of the brushed handles: {ms_pose:.3f} ms", flush=True)
+    return {"brushes": brushes, "brush_vertices": seeds, "brush_handle_sizes": sizes, "brush_rounds": [s["rounds"] for s in stats],
+            "brush_calls": [s["calls"] for s in stats], "ms_per_brush_set": round(ms_brush, 4), "ms_per_brushed_pose": round(ms_pose, 4)}
+
+
 def _normals_fields(ms_drag, ms_normals, faces):
     return {"normals": True, "faces": faces, "ms_per_drag_normals": round(ms_normals, 4),
             "normals_ms": round(ms_normals - ms_drag, 4), "normals_over_drag": round(ms_normals / ms_drag, 4) if ms_drag > 0 else None}
@@ -1581,8 +1731,8 @@ def main_ragged(args, vertex_counts, surface_counts):
 def handles_from_args(args):
     """(--handles as a list of part names, --axis as three floats); (None, None) without --handles."""
     if args.handles is None:
-        if args.track is not None or args.rotate_deg:
-            sys.exit("nsdp_amd.edit: --track and --rotate-deg go with --handles")
+        if args.track is not None or (args.rotate_deg and not args.brush):
+            sys.exit("nsdp_amd.edit: --track and --rotate-deg go with --handles (--rotate-deg with --brush too)")
         return None, None
     names = [p for p in args.handles.split(",") if p]
     if not names or any(p not in PARTS for p in names) or len(set(names)) != len(names):
@@ -1665,6 +1815,7 @@ def main_handles(args, names, axis):
 
 def main(argv=None):
     args = build_parser().parse_args(list(sys.argv[1:] if argv is None else argv))
+    brushes = brushes_from_args(args)
     vertex_counts, surface_counts = counts_from_args(args)
     names, axis = handles_from_args(args)
     if names is not None:
@@ -1674,6 +1825,8 @@ def main(argv=None):
             sys.exit("nsdp_amd.edit: --self-intersections times drags by rule (--part), not --handles")
         if args.pick is not None:
             sys.exit("nsdp_amd.edit: --pick goes with drags by rule (--part), not --handles")
+        if brushes is not None:
+            sys.exit("nsdp_amd.edit: --brush makes its own handles: not with --handles")
         if vertex_counts is not None:
             sys.exit("nsdp_amd.edit: --handles goes with --vertices / --batch, not with --vertex-counts")
         if args.vertices < 1 or (args.surface is not None and args.surface < 1) or args.drags < 1:
@@ -1684,11 +1837,13 @@ def main(argv=None):
             sys.exit("nsdp_amd.edit: --surface and --drags want positive integers")
         if args.pick is not None:
             sys.exit("nsdp_amd.edit: --pick goes with --vertices / --batch, not with --vertex-counts")
+        if brushes is not None:
+            sys.exit("nsdp_amd.edit: --brush goes with --vertices / --batch, not with --vertex-counts")
         return main_ragged(args, vertex_counts, surface_counts)
     ray = pick_from_args(args)
     if args.vertices < 1 or (args.surface is not None and args.surface < 1) or args.drags < 1:
         sys.exit("nsdp_amd.edit: --vertices, --surface and --drags want positive integers")
-    sphere = sphere_for(args.vertices) if args.normals or args.self_intersections or ray is not None else None
+    sphere = sphere_for(args.vertices) if args.normals or args.self_intersections or ray is not None or brushes is not None else None
     if sphere is not None:
         args.vertices = int(sphere[0].shape[0])
     device, config, spec, model, test_fn, timed, translation = _setup(args, args.surface or args.vertices)
@@ -1718,6 +1873,7 @@ def main(argv=None):
         selfint_fields = _timed_with_self_intersections(args, session, spec, translation, timed, max(args.warmup, 1))
         out = session.drag(spec.part, translation(args.drags - 1), with_inputs=True)
         pick_fields = _picked(ray, session, out, batch, device, timed, args.drags)
+        pick_fields.update(_brushed(brushes, session, args, spec, batch, device, timed))
         dd = {"surface_samples_inputs": out["surface_samples_inputs"], "verts_src": verts,
               "surface_samples_src": out["surface_samples_inputs"][:, :, 0:3].contiguous()}
         for _ in range(max(args.warmup, 1)):
