@@ -17,6 +17,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.path.join(_HERE, "lib", "libnsdp_hip.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "nsdp_hip.h")
+RASTER_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "nsdp_raster.h")      # (the rasteriser's entries: their own header)
 
 _lib = None
 

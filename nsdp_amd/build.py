@@ -35,6 +35,7 @@ MESHNORMALS_HEADER = os.path.join(os.path.dirname(HERE), "include", "nsdp_meshno
 SELFINTERSECT_HEADER = os.path.join(os.path.dirname(HERE), "include", "nsdp_selfintersect.h")
 RAYCAST_HEADER = os.path.join(os.path.dirname(HERE), "include", "nsdp_raycast.h")
 GEODESIC_HEADER = os.path.join(os.path.dirname(HERE), "include", "nsdp_geodesic.h")
+RASTER_HEADER = os.path.join(os.path.dirname(HERE), "include", "nsdp_raster.h")
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # -munsafe-fp-atomics: fp32 atomicAdd lowers to the hardware global_atomic_add_f32 instead of a CAS loop
@@ -64,6 +65,7 @@ PER_FILE = {
     "self_intersect.hip": EXACT,                # (the rule of nsdp_selfintersect.h: the signs of determinants, one rounding per operation)
     "ray_cast.hip": EXACT,                      # (the rule of nsdp_raycast.h: fp32 shear, exact fp64 edge signs, one rounding per operation)
     "geodesic.hip": EXACT,                      # (the rule of nsdp_geodesic.h: edge lengths and path sums, one rounding per operation, exact sqrt)
+    "rasterize.hip": EXACT,                     # (the rule of nsdp_raster.h: fp32 corners, exact integer edge signs in fp64, one rounding per operation)
     "pointnet2_ops.hip": EXACT,
     # torch's single-tensor Adam rounds once per operation: no fused multiply-adds in the optimizer kernel (nor in the
     # gradient-norm kernels of nsdp_optim.h, which live beside it and share its chunk loop)
@@ -85,7 +87,7 @@ def sources():
 
 def _deps_mtime():
     # (this file too: the compiler flags live here)
-    hs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")] + [HEADER, EVAL_HEADER, SAMPLING_HEADER, SEARCH_HEADER, SCATTER_HEADER, HANDLES_HEADER, HANDLES_RAGGED_HEADER, HANDLE_SETS_HEADER, CHAMFER_HEADER, JACOBIAN_HEADER, RIGIDITY_HEADER, SURFACE_HEADER, BATCH_HEADER, MESHBATCH_HEADER, MESHWHOLE_HEADER, OPTIM_HEADER, MESHNORMALS_HEADER, SELFINTERSECT_HEADER, RAYCAST_HEADER, GEODESIC_HEADER, os.path.abspath(__file__)]
+    hs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")] + [HEADER, EVAL_HEADER, SAMPLING_HEADER, SEARCH_HEADER, SCATTER_HEADER, HANDLES_HEADER, HANDLES_RAGGED_HEADER, HANDLE_SETS_HEADER, CHAMFER_HEADER, JACOBIAN_HEADER, RIGIDITY_HEADER, SURFACE_HEADER, BATCH_HEADER, MESHBATCH_HEADER, MESHWHOLE_HEADER, OPTIM_HEADER, MESHNORMALS_HEADER, SELFINTERSECT_HEADER, RAYCAST_HEADER, GEODESIC_HEADER, RASTER_HEADER, os.path.abspath(__file__)]
     return max(os.path.getmtime(h) for h in hs)
 
 

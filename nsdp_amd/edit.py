@@ -1,7 +1,8 @@
 """Editing session: drag handles on a mesh without re-encoding its source.
 
     python -m nsdp_amd.edit CONFIG [--vertices N] [--surface N] [--batch B] [--part P --translate dx,dy,dz] [--drags K]
-                                   [--graph] [--normals] [--self-intersections] [--weight_file F] [--out DIR]
+                                   [--graph] [--normals] [--self-intersections] [--render OUT.png [--render-size S]]
+                                   [--weight_file F] [--out DIR]
     python -m nsdp_amd.edit CONFIG --vertex-counts n1,n2,... [--surface-counts s1,s2,... | --surface N] [--graph] ...
 
 The reference's interactive editing (run.py, "Interactive Editing / Run-batch-processing"; config/tosca/*.yaml,
@@ -70,6 +71,15 @@ by the work guard), ``tgt_self_intersections`` (the intersecting pairs of every 
 Every stage of a drag is the kernel the step function runs, on the same operands: the predictions are bit-equal to
 ``test_on_batch_with_arbitrary`` (``test_on_batch_with_cano`` for a single network) on the data_dict the drag stands for
 (tests/test_edit_session_gpu.py, tests/test_edit_session_ragged_gpu.py).
+
+Previews (nsdp_amd/rasterize.py, include/nsdp_raster.h): a session opened with ``faces`` takes ``drag / pose / track(...,
+render=RenderSpec(cameras, height, width, shade=True, count=False))`` and adds ``tgt_depth`` and ``tgt_face_image`` [.., K, H, W],
+``tgt_dropped`` [.., K] and, with ``shade``, the uint8 ``tgt_image`` [.., K, H, W, 3] of the deformed meshes -- three launches and
+the shading's gathers behind the decode, inside the captured graph, a graph of its own per RenderSpec.  The predictions are the
+same bits either way.  There is no near-plane clipping: ``tgt_dropped`` counts the faces that reach the camera plane.
+``session.render(cameras, height, width, verts=None)`` draws the source mesh or given vertices.
+
+    python -m nsdp_amd.edit CONFIG --vertices N --render OUT.png [--render-size S] [--graph]      # a sphere mesh, one fitted view
 """
 from __future__ import annotations
 
@@ -81,6 +91,21 @@ from dataclasses import dataclass
 
 PARTS = ("head", "tail", "frontleftfoot", "frontrightfoot", "behindleftfoot", "behindrightfoot")      # the reference's priority
 SEED_DATA, SEED_WEIGHTS = 1000, 2048      # (nsdp_amd.infer's)
+
+
+@dataclass(eq=False)
+class RenderSpec:
+    """A preview of every deformed mesh behind a drag (nsdp_amd/rasterize.py, include/nsdp_raster.h): ``cameras`` -- a
+    ``Camera``, a sequence of K of them, or a float32 GPU tensor [K, 4, 4] (the same K views of every mesh) or [..., K, 4, 4] --
+    and the image's ``height`` and ``width``.  ``shade``: the head-light image ``tgt_image`` beside the depth and face images;
+    ``count``: the per-pixel number of covering faces too.  One object per view set: the session keys its captured graph by it,
+    and a graph reads the camera tensor where it lies -- write new matrices into ``tensor`` in place to move the camera."""
+    cameras: object
+    height: int
+    width: int
+    shade: bool = True
+    count: bool = False
+    tensor: object = None       # the cameras on the session's device, made at the first use
 
 
 @dataclass(frozen=True)
@@ -374,7 +399,7 @@ class _Session:
     def _open_normals(self):
         """The last step of ``_open`` (outside any capture): the topology of ``faces`` over the vertices' layout -- the corner
         lists, one host read -- and the source mesh's normals.  Without faces the session holds neither."""
-        self.topology = self.verts_src_normals = self.selfint_plan = self.pick_plan = self.brush_plan = None
+        self.topology = self.verts_src_normals = self.selfint_plan = self.pick_plan = self.brush_plan = self.render_plan = None
         if self.faces is not None:
             from .mesh_normals import MeshTopology, vertex_normals
             self.topology = MeshTopology(self.faces, self.verts)
@@ -450,6 +475,52 @@ class _Session:
         out["verts_tgt_normals"] = vertex_normals(verts if lead is None else verts.view(lead + tuple(verts.shape[-2:])), self.topology)
         return out
 
+    # ------------------------------------------------------------------ previews
+    def _render_wanted(self, what, render):
+        """``render=RenderSpec(...)`` needs the faces; the plan (the faces in Morton order of the source mesh, no host read: the
+        topology is validated) and the spec's camera tensor are made at the first such call, outside any capture."""
+        if render is None:
+            return None
+        if not isinstance(render, RenderSpec):
+            raise ValueError(f"{what}: render must be a RenderSpec(cameras, height, width), got {type(render).__name__}")
+        if self.topology is None:
+            raise ValueError(self._refused + f"{what}(render=...) without faces: the session was opened without `faces`, and a "
+                             "rasteriser draws the mesh's triangles -- open it with faces=...")
+        from .rasterize import RasterPlan, camera_tensor
+        if self.render_plan is None:
+            self.render_plan = RasterPlan(self.faces, self.verts, topology=self.topology)
+        if render.tensor is None:
+            render.tensor = camera_tensor(render.cameras, self.topology.device)
+            if hasattr(render.tensor, "contiguous"):
+                render.tensor = render.tensor.contiguous()
+        return render
+
+    def _with_render(self, pred, spec, lead=None):
+        """``pred`` with the images of its vertices (no near-plane clipping: ``tgt_dropped`` counts the faces that reach the
+        camera plane): three launches behind the decode, and the shading's gathers.  The predictions are not touched."""
+        from .rasterize import rasterize, shade
+        verts = pred["verts_tgt_pred"]
+        verts = verts if lead is None else verts.view(lead + tuple(verts.shape[-2:]))
+        r = rasterize(verts, self.render_plan, spec.tensor, spec.height, spec.width, return_bary=spec.shade, count=spec.count)
+        out = dict(pred)
+        out["tgt_depth"], out["tgt_face_image"], out["tgt_dropped"] = r.depth, r.face, r.dropped
+        if spec.count:
+            out["tgt_count_image"] = r.count
+        if spec.shade:
+            out["tgt_image"] = shade(r, verts, self.render_plan, normals=pred.get("verts_tgt_normals"))
+        return out
+
+    def render(self, cameras, height, width, verts=None, shade=True, count=False):
+        """The source mesh, or ``verts`` -- a vertex set of the same topology such as a drag's ``verts_tgt_pred`` -- under
+        ``cameras`` (what ``RenderSpec`` takes): ``tgt_depth``, ``tgt_face_image`` [.., K, H, W], ``tgt_dropped`` [.., K] and with
+        ``shade`` the uint8 ``tgt_image`` [.., K, H, W, 3].  A call of its own, no part of a drag's graph."""
+        import torch
+        spec = self._render_wanted("render", RenderSpec(cameras, height, width, shade, count))
+        v = self.verts if verts is None else verts
+        with torch.no_grad():
+            out = self._with_render({"verts_tgt_pred": v.packed if hasattr(v, "packed") else v}, spec)
+        return {k: out[k] for k in ("tgt_depth", "tgt_face_image", "tgt_dropped", "tgt_count_image", "tgt_image") if k in out}
+
     # ------------------------------------------------------------------ one drag
     def _mask_buffer(self, name, like_rows, value, device):
         import torch
@@ -465,7 +536,7 @@ class _Session:
 
     def drag(self, part=None, translation=(0.0, 0.0, 0.0), handle_mask=None, move_mask=None, vert_handle_mask=None,
              vert_move_mask=None, partial_range=None, cliptail=None, with_inputs=False, clone=True, normals=False,
-             self_intersections=False):
+             self_intersections=False, render=None):
         """One drag of every shape.  By rule: ``part`` (a name of PARTS, one per shape, or a HandleSpec) moves by ``translation``
         ((dx, dy, dz) or [B, 3]).  By explicit regions: ``handle_mask`` / ``move_mask`` over the cloud (bool / uint8 on the GPU:
         [B, n] for a rectangular cloud, (scap,) for a packed one) replace the rule; with a separate cloud ``vert_handle_mask`` /
@@ -479,11 +550,15 @@ class _Session:
         ``verts_tgt_normals``, the unit vertex normals of ``verts_tgt_pred`` in its shape.  ``self_intersections=True`` (faces
         too) adds ``faces_tgt_hits`` (per face the faces it passes through, -1: skipped by the work guard),
         ``tgt_self_intersections`` (int64, the intersecting pairs of every mesh) and ``tgt_self_skipped`` -- the fields of
-        ``nsdp_amd.self_intersect.self_intersections`` on ``verts_tgt_pred``."""
+        ``nsdp_amd.self_intersect.self_intersections`` on ``verts_tgt_pred``.  ``render=RenderSpec(cameras, height, width)``
+        (faces too) adds ``tgt_depth`` and ``tgt_face_image`` [.., K, H, W], ``tgt_dropped`` [.., K] (the faces that reach the
+        camera plane: there is no near-plane clipping) and, with the spec's ``shade``, the uint8 ``tgt_image`` [.., K, H, W, 3]
+        -- ``nsdp_amd.rasterize.rasterize`` on ``verts_tgt_pred``, inside the captured graph."""
         import torch
         from ._lib import on_device
         normals = self._normals_wanted("drag", normals)
         selfint = self._selfint_wanted("drag", self_intersections)
+        render = self._render_wanted("drag", render)
         if torch.is_grad_enabled():
             raise ValueError(self._refused + "autograd is enabled -- drag under torch.no_grad()")
         if self.model.training:
@@ -519,28 +594,34 @@ class _Session:
                     self._mask_buffer("_vmask_h", vert_rows, vert_handle_mask, on.device)
                     self._mask_buffer("_vmask_m", vert_rows, vert_move_mask, on.device)
             key = (masks, vert_masks)
-            pred = self._dispatch_normals(key, lambda: self._enqueue(*key), normals, selfint=selfint)
+            pred = self._dispatch_normals(key, lambda: self._enqueue(*key), normals, selfint=selfint, render=render)
             own, own_pred = self._owners(clone)
             return self._add_normals(self._result(pred, own, own_pred, self.same or not masks or vert_masks, with_inputs), pred, own_pred)
 
-    def _dispatch_normals(self, key, enqueue, normals, lead=None, selfint=False):
+    def _dispatch_normals(self, key, enqueue, normals, lead=None, selfint=False, render=None):
         """``_dispatch``; with ``normals`` the vertex normals behind the same work, with ``selfint`` the self-intersections,
-        each under a key of its own (another graph): calls without the flags keep their graph and their bits."""
-        if not normals and not selfint:
+        with ``render`` the images, each under a key of its own (another graph): calls without the flags keep their graph and
+        their bits."""
+        if not normals and not selfint and render is None:
             return self._dispatch(key, enqueue)
 
         def work():
             pred = enqueue()
             if normals:
                 pred = self._with_normals(pred, lead)
+            if render is not None:
+                pred = self._with_render(pred, render, lead)
             return self._with_self_intersections(pred, lead) if selfint else pred
-        return self._dispatch(key + (("normals",) if normals else ()) + (("self_intersections",) if selfint else ()), work)
+        return self._dispatch(key + (("normals",) if normals else ()) + (("self_intersections",) if selfint else ()) +
+                              (("render", id(render), render.height, render.width, render.shade, render.count) if render is not None
+                               else ()), work)
 
     def _add_normals(self, out, pred, own_pred, shape=None):
         if "verts_tgt_normals" in pred:
             n = own_pred(pred["verts_tgt_normals"])
             out["verts_tgt_normals"] = self._over_verts(n if shape is None else n.view(shape))
-        for name in ("faces_tgt_hits", "tgt_self_intersections", "tgt_self_skipped"):
+        for name in ("faces_tgt_hits", "tgt_self_intersections", "tgt_self_skipped", "tgt_depth", "tgt_face_image", "tgt_dropped",
+                     "tgt_count_image", "tgt_image"):
             if name in pred:
                 out[name] = own_pred(pred[name])
         return out
@@ -643,17 +724,18 @@ class _Session:
         return not self.same and self._vert_labelled and (targets is None or vert_targets is not None)
 
     def pose(self, motions=None, targets=None, vert_targets=None, with_inputs=False, clone=True, normals=False,
-             self_intersections=False):
+             self_intersections=False, render=None):
         """One pose of every shape's labelled handle set (``set_handles``).  ``motions``: anything ``pack_motions`` takes -- one
         list of H motions for every shape, a list per shape, or a [B, H, 12] array; one host-to-device copy.  ``targets``: a
         target per cloud point instead, a float32 GPU tensor over the cloud's layout with 3 columns ([B, n, 3]; (scap, 3)),
         read at the handle points only; ``vert_targets`` the same for the vertices of a separate cloud.  Returns what ``drag``
         returns, in the same shapes (``normals=True``: with ``verts_tgt_normals``; ``self_intersections=True``: with ``drag``'s
-        three fields)."""
+        three fields; ``render=RenderSpec(...)``: with ``drag``'s images)."""
         import torch
         from ._lib import on_device
         normals = self._normals_wanted("pose", normals)
         selfint = self._selfint_wanted("pose", self_intersections)
+        render = self._render_wanted("pose", render)
         vert = self._pose_checks("pose", motions, targets, vert_targets)
         B, on, cloud_rows, vert_rows = self._layout()
         if targets is None:
@@ -670,7 +752,7 @@ class _Session:
                 if vert:
                     self._session_copy("_vtargets", vert_targets)
             key = ("pose", targets is not None, vert)
-            pred = self._dispatch_normals(key, lambda: self._enqueue_pose(*key[1:]), normals, selfint=selfint)
+            pred = self._dispatch_normals(key, lambda: self._enqueue_pose(*key[1:]), normals, selfint=selfint, render=render)
             own, own_pred = self._owners(clone)
             return self._add_normals(self._result(pred, own, own_pred, self.same or vert, with_inputs), pred, own_pred)
 
@@ -792,7 +874,7 @@ class _Session:
     def close(self):
         self._drop_graphs()
         self._forget_handles()
-        for name in self._cached + ("topology", "verts_src_normals", "selfint_plan", "pick_plan", "brush_plan"):
+        for name in self._cached + ("topology", "verts_src_normals", "selfint_plan", "pick_plan", "brush_plan", "render_plan"):
             setattr(self, name, None)
 
     def __enter__(self):
@@ -945,7 +1027,7 @@ class EditSession(_Session):
         return self._network(st.buf, st.geometry, st.verts2cano, st.surf2cano, st.surf_idx)
 
     def track(self, motions=None, targets=None, vert_targets=None, with_inputs=False, clone=True, normals=False,
-              self_intersections=False):
+              self_intersections=False, render=None):
         """T poses of the labelled handle set in one call: ``motions`` [T, B, H, 12] or a list of T ``pack_motions`` inputs, or
         ``targets`` [T, B, n, 3] on the GPU (``vert_targets`` [T, B, V, 3] for the vertices of a separate cloud).  One launch of
         the labelled kernel writes the T * B input rows, network 2 runs once over them; a drag of a small mesh is bound by its
@@ -954,7 +1036,8 @@ class EditSession(_Session):
         Returns ``verts_tgt_pred`` and ``verts_tgt`` [T, B, V, 3], ``surface_samples_tgt_pred`` [T, B, S, 3], the handle masks
         [B, .] (they do not depend on the pose) and with ``with_inputs`` ``surface_samples_inputs`` [T, B, S, 7]; with
         ``normals=True`` ``verts_tgt_normals`` [T, B, V, 3] -- the T * B poses in the same two launches; with
-        ``self_intersections=True`` ``faces_tgt_hits`` [T, B, F], ``tgt_self_intersections`` and ``tgt_self_skipped`` [T, B].
+        ``self_intersections=True`` ``faces_tgt_hits`` [T, B, F], ``tgt_self_intersections`` and ``tgt_self_skipped`` [T, B];
+        with ``render=RenderSpec(...)`` ``tgt_depth`` and ``tgt_face_image`` [T, B, K, H, W] and ``drag``'s other images.
 
         A track shares with the session network 1's outputs, the labels and the handle masks; its input rows, its index sets
         (those of the session's, over T * B rows) and its graphs -- one per (form, T) -- are its own and are made at the first
@@ -965,6 +1048,7 @@ class EditSession(_Session):
         from ._lib import on_device
         normals = self._normals_wanted("track", normals)
         selfint = self._selfint_wanted("track", self_intersections)
+        render = self._render_wanted("track", render)
         vert = self._pose_checks("track", motions, targets, vert_targets)
         B, S, V, H = self.surface.shape[0], self.surface.shape[1], self.verts.shape[1], self._count
         if targets is not None:
@@ -1000,7 +1084,8 @@ class EditSession(_Session):
                             setattr(st, name, torch.empty_like(value, memory_format=torch.contiguous_format))
                         getattr(st, name).copy_(value, non_blocking=True)
             key = ("track", T, targets is not None, vert)
-            pred = self._dispatch_normals(key, lambda: self._enqueue_track(*key[1:]), normals, lead=(T, B), selfint=selfint)
+            pred = self._dispatch_normals(key, lambda: self._enqueue_track(*key[1:]), normals, lead=(T, B), selfint=selfint,
+                                          render=render)
             own, own_pred = self._owners(clone)
             have_verts = self.same or vert
             out = {"verts_tgt_pred": own_pred(pred["verts_tgt_pred"]).view(T, B, V, 3)}
@@ -1413,6 +1498,10 @@ def build_parser():
                     help="(repeatable) on the sphere mesh of --normals: pick the vertex the ray from (ox, oy, oz) along (dx, dy, dz) "
                          "meets and brush a handle of that geodesic radius around it (labels_from_brush); the handles are set and "
                          "posed -- the first by --rotate-deg about its centroid plus --translate, the others pinned")
+    ap.add_argument("--render", default=None, metavar="OUT.png",
+                    help="drag the sphere mesh of --normals with a preview (render=RenderSpec: one fitted view of every deformed "
+                         "mesh, rasterised behind the decode) and write the first mesh's shaded image of the last drag as a PNG")
+    ap.add_argument("--render-size", type=int, default=512, dest="render_size", metavar="S", help="the preview is S x S pixels")
     ap.add_argument("--weight_file", default=None, help="weights of the whole model (default: procedural weights)")
     ap.add_argument("--out", default=None, help="directory for the last drag's predictions (<key>.npy)")
     return ap
@@ -1517,6 +1606,26 @@ def _timed_with_normals(args, session, spec, translation, timed, warm):
     for i in range(warm):
         session.drag(spec.part, translation(i), normals=True)
     return timed(lambda i: session.drag(spec.part, translation(i), clone=False, normals=True), args.drags)
+
+
+def _timed_with_render(args, session, verts, spec, translation, timed, warm, ms_drag):
+    """--render: the same drags with ``render=RenderSpec(...)`` (--graph: a graph of its own), the camera fitted to the first
+    drag's prediction (one host read, before the timed drags), the last drag's first image written as a PNG -> the JSON fields;
+    {} without."""
+    if not args.render:
+        return {}
+    from .rasterize import Camera, write_png
+    size = args.render_size
+    view = RenderSpec(Camera.fit(session.drag(spec.part, translation(0))["verts_tgt_pred"], (0.3, -0.2, 1.0), size, size), size, size)
+    for i in range(warm):
+        session.drag(spec.part, translation(i), render=view)
+    ms = timed(lambda i: session.drag(spec.part, translation(i), clone=False, render=view), args.drags)
+    out = session.drag(spec.part, translation(args.drags - 1), render=view)
+    image = out["tgt_image"].reshape((-1, size, size, 3))[0]
+    write_png(args.render, image)
+    return {"render": args.render, "render_size": size, "ms_per_drag_render": round(ms, 4), "render_ms": round(ms - ms_drag, 4),
+            "render_over_drag": round(ms / ms_drag, 4) if ms_drag > 0 else None,
+            "render_covered": int((out["tgt_face_image"] >= 0).sum()), "render_dropped": int(out["tgt_dropped"].sum())}
 
 
 def _timed_with_self_intersections(args, session, spec, translation, timed, warm):
@@ -1825,6 +1934,8 @@ def main(argv=None):
             sys.exit("nsdp_amd.edit: --self-intersections times drags by rule (--part), not --handles")
         if args.pick is not None:
             sys.exit("nsdp_amd.edit: --pick goes with drags by rule (--part), not --handles")
+        if args.render:
+            sys.exit("nsdp_amd.edit: --render goes with drags by rule (--part), not --handles")
         if brushes is not None:
             sys.exit("nsdp_amd.edit: --brush makes its own handles: not with --handles")
         if vertex_counts is not None:
@@ -1837,13 +1948,18 @@ def main(argv=None):
             sys.exit("nsdp_amd.edit: --surface and --drags want positive integers")
         if args.pick is not None:
             sys.exit("nsdp_amd.edit: --pick goes with --vertices / --batch, not with --vertex-counts")
+        if args.render:
+            sys.exit("nsdp_amd.edit: --render goes with --vertices / --batch, not with --vertex-counts")
         if brushes is not None:
             sys.exit("nsdp_amd.edit: --brush goes with --vertices / --batch, not with --vertex-counts")
         return main_ragged(args, vertex_counts, surface_counts)
     ray = pick_from_args(args)
     if args.vertices < 1 or (args.surface is not None and args.surface < 1) or args.drags < 1:
         sys.exit("nsdp_amd.edit: --vertices, --surface and --drags want positive integers")
-    sphere = sphere_for(args.vertices) if args.normals or args.self_intersections or ray is not None or brushes is not None else None
+    if args.render and not 1 <= args.render_size <= 4096:
+        sys.exit(f"nsdp_amd.edit: --render-size wants 1 .. 4096 pixels, got {args.render_size}")
+    sphere = sphere_for(args.vertices) if (args.normals or args.self_intersections or ray is not None or brushes is not None
+                                           or args.render) else None
     if sphere is not None:
         args.vertices = int(sphere[0].shape[0])
     device, config, spec, model, test_fn, timed, translation = _setup(args, args.surface or args.vertices)
@@ -1871,6 +1987,7 @@ def main(argv=None):
         ms_drag = timed(lambda i: out.update(session.drag(spec.part, translation(i), clone=False)), args.drags)
         ms_normals = _timed_with_normals(args, session, spec, translation, timed, max(args.warmup, 1))
         selfint_fields = _timed_with_self_intersections(args, session, spec, translation, timed, max(args.warmup, 1))
+        selfint_fields.update(_timed_with_render(args, session, verts, spec, translation, timed, max(args.warmup, 1), ms_drag))
         out = session.drag(spec.part, translation(args.drags - 1), with_inputs=True)
         pick_fields = _picked(ray, session, out, batch, device, timed, args.drags)
         pick_fields.update(_brushed(brushes, session, args, spec, batch, device, timed))

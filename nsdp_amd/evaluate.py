@@ -20,7 +20,8 @@ Output, in the experiment directory:
   <motion_split>/<mesh_folder>/{source,canonical,deformed,target,handle}/   with ``test.generate_mesh``: the meshes through
                         ``meshio.write_mesh`` under the reference's file names (utils/generation.py:11-35), vertices grey 0.75,
                         handle vertices red on source and canonical and blue on target; the handle mesh is the target's faces
-                        whose three vertices are all handles; the deformed mesh is written uncoloured (no error colour map).
+                        whose three vertices are all handles; the deformed mesh is written uncoloured unless
+                        ``test.vert_pred_color`` is set (below).
 A pair's ``loss`` is what the step function returns for the BATCH the pair was in (the mean over its shapes of
 compute_l2_error); at ``--batch 1`` it is the pair's own, as in the reference.
 
@@ -50,6 +51,19 @@ Volume IoU, opt-in (nsdp_amd/ray_cast.py; without the key the files are byte for
                                           ``.tolist()``, with a plain mean.  Inside is the parity of ray crossings: it means
                                           something on closed meshes only, so a batch with open edges gets a WARNING line that
                                           names its pairs.
+
+Error colours and views, opt-in (nsdp_amd/rasterize.py; without the keys the files are byte for byte what they were):
+  test.vert_pred_color: true              with ``test.generate_mesh`` the deformed mesh is written with per-vertex colours, the jet
+                                          map of |pred - tgt| clipped at 0.2 (``rasterize.error_colors``: the reference's
+                                          generate_meshes(..., vert_pred_color=True)); they are computed on the device and travel in
+                                          the batch's ONE device-to-host copy of the meshes;
+  test.render: {views: K, size: S}        writes <motion_split>/<render_folder>/<src>_to_<tgt>_view<k>.png, K (1 .. 6) views of
+                                          S x S pixels of every PREDICTED mesh, shaded with the error colours, rasterised on the
+                                          device.  The cameras are fitted to the pair's TARGET mesh (its bounding box, read back once
+                                          per batch) from the fixed directions ``VIEW_DIRECTIONS``: a function of the data and the
+                                          config only.  ``dropped``, the faces the views lost over all K (a face that reaches the
+                                          camera plane is dropped whole: there is no near-plane clipping; 0 for these fitted
+                                          orthographic cameras unless a vertex is not finite), goes into the pair's row.
 
 Refused by name: ``test.generate_pointcloud`` (point-cloud export).  Out of scope: ``--gpus N``, graph replay of the whole step.
 """
@@ -192,10 +206,46 @@ def batch_volume_iou(faces, pred, target, points, seed, step):
     return {"iou": iou, "iou_open": plan.open_edges_per_mesh.double()}
 
 
-def export_meshes(directory, pair_infos, ext, verts, handle, faces, vert_counts, face_counts, normals=None):
+VIEW_DIRECTIONS = ((0.3, -0.2, 1.0), (-1.0, -0.2, 0.3), (0.3, -0.2, -1.0), (1.0, -0.2, -0.3), (0.2, -1.0, 0.2), (0.2, 1.0, -0.2))
+
+
+def render_settings(test):
+    """(views, size) of ``test.render``; (0, 0) without the key."""
+    cfg = test.get("render")
+    if not cfg:
+        return 0, 0
+    views, size = (cfg.get("views", 1), cfg.get("size", 512)) if isinstance(cfg, dict) else (None, None)
+    ok = lambda v, top: isinstance(v, int) and not isinstance(v, bool) and 1 <= v <= top
+    if not ok(views, len(VIEW_DIRECTIONS)) or not ok(size, 4096):
+        raise EvaluateError(f"evaluate: test.render = {cfg!r}: {{views: 1 .. {len(VIEW_DIRECTIONS)}, size: 1 .. 4096}}")
+    return views, size
+
+
+def batch_views(faces, pred, target, colors, views, size):
+    """(uint8 [B, views, size, size, 3] on the host, dropped [B][views]) of a batch: every predicted mesh (RaggedPoints) under
+    ``views`` orthographic cameras fitted to its TARGET mesh from ``VIEW_DIRECTIONS``, shaded with the per-vertex ``colors``
+    [cap, 3].  One read-back of the targets' bounding boxes, one of the images, one of the counts.  The store has clamped every
+    face index into its mesh, so nothing is read back to validate them."""
+    from .rasterize import Camera, RasterPlan, rasterize, shade
+    from .ragged import shape_ids
+    B, t = target.batch, target.packed.detach()
+    where = shape_ids(target.offsets, target.capacity).unsqueeze(1).expand(-1, 3)
+    lo = torch.full((B + 1, 3), float("inf"), device=t.device).scatter_reduce(0, where, t, "amin")[:B]
+    hi = torch.full((B + 1, 3), float("-inf"), device=t.device).scatter_reduce(0, where, t, "amax")[:B]
+    box = torch.stack([lo, hi]).cpu().numpy()
+    cams = np.stack([[Camera.fit_box(box[0, b], box[1, b], VIEW_DIRECTIONS[k], size, size).matrix for k in range(views)]
+                     for b in range(B)])
+    verts = pred.like(pred.packed.detach())
+    plan = RasterPlan(faces, verts, validate=False)
+    r = rasterize(verts, plan, torch.from_numpy(cams).to(t.device), size, size)
+    return shade(r, verts, plan, colors=colors).cpu().numpy(), r.dropped.tolist()
+
+
+def export_meshes(directory, pair_infos, ext, verts, handle, faces, vert_counts, face_counts, normals=None, deformed_colors=None):
     """Write the meshes of a batch that is already on the host.  ``verts``: part -> [cap, 3] fp32 for "source", "deformed",
     "target" and, where it is exported, "canonical"; ``handle`` [cap] bool; ``faces`` [fcap, 3] int32, local indices;
-    ``normals``: part -> [cap, 3] fp32 for the parts that are written with normals."""
+    ``normals``: part -> [cap, 3] fp32 for the parts that are written with normals; ``deformed_colors``: [cap, 3] uint8 for
+    the deformed mesh (written uncoloured without)."""
     from .meshio import write_mesh
     normals = normals or {}
     v0 = f0 = 0
@@ -208,6 +258,8 @@ def export_meshes(directory, pair_infos, ext, verts, handle, faces, vert_counts,
                                       ("target", "target", blue, f), ("handle", "target", blue, f[h[f].all(axis=1)])):
             if verts.get(of) is None:
                 continue
+            if part == "deformed" and deformed_colors is not None:
+                colors = np.ascontiguousarray(deformed_colors[v0:v0 + nv])
             path = os.path.join(directory, names[part])
             os.makedirs(os.path.dirname(path), exist_ok=True)
             if normals.get(part) is None:
@@ -242,6 +294,9 @@ def evaluate(model, test_fn, store, config, experiment_directory, batch, seed, l
     if isinstance(iou_points, bool) or not isinstance(iou_points, int) or iou_points < 0:
         raise EvaluateError(f"evaluate: test.volume_iou = {test.get('volume_iou')!r}: the samples per pair, a positive integer "
                             "(not true / false)")
+    with_colors = bool(test.get("vert_pred_color")) and mesh_dir is not None
+    views, size = render_settings(test)
+    render_dir = os.path.join(experiment_directory, split, test.get("render_folder", "renders")) if views else None
     metrics = METRICS + (("vnc",) if with_vnc else ())
     read = metrics + ((SI_KEYS + ("si_skipped",)) if with_si else ()) + (("iou", "iou_open") if iou_points else ())
     # (read: what the batch's one read-back carries)
@@ -268,6 +323,16 @@ def evaluate(model, test_fn, store, config, experiment_directory, batch, seed, l
             else:
                 values = torch.stack([m[k] for k in METRICS]).tolist()      # the batch's ONE read-back of metrics
             infos = [store.pairs[i] for i in out["index"]]
+            if with_colors or views:
+                from .rasterize import error_colors, to_uint8, vertex_errors, write_png
+                colors = error_colors(vertex_errors(pred.packed, out["verts_tgt"].packed))
+            if views:
+                images, dropped = batch_views(faces, pred, out["verts_tgt"], colors, views, size)
+                os.makedirs(render_dir, exist_ok=True)
+                for b, info in enumerate(infos):
+                    stem = os.path.splitext(os.path.basename(export_names(info, "png")["deformed"]))[0]
+                    for k in range(views):
+                        write_png(os.path.join(render_dir, f"{stem}_view{k}.png"), images[b, k])
             if iou_points:
                 at_iou = len(read) - 2
                 not_closed = [int(out["index"][b]) for b in range(len(infos)) if values[at_iou + 1][b]]
@@ -289,15 +354,21 @@ def evaluate(model, test_fn, store, config, experiment_directory, batch, seed, l
                 if iou_points:
                     row["iou"] = values[at_iou][b]
                     tail += "  iou {:.6e}".format(row["iou"])
+                if views:
+                    row["dropped"] = int(sum(dropped[b]))
+                    tail += "  dropped {:d}".format(row["dropped"])
                 rows.append(row)
                 say("pair {:5d} {}_{} -> {}_{}  loss {:.6e}  ".format(row["index"], info[4], info[5], info[6], info[7], row["loss"])
                     + "  ".join("{} {:.6e}".format(k, row[k]) for k in metrics) + tail)
             if mesh_dir is not None:
                 extra = [n_src, n_pred, n_tgt] if with_normals else []      # (in the same copy)
+                if with_colors:                                             # (and the colours: bytes widened to words for the trip)
+                    extra = extra + [to_uint8(colors).to(torch.int32).view(torch.float32)]
                 sets, handle, f = _to_host([out["verts_src"].packed, out["verts_cano"].packed, pred.packed.detach(),
                                             out["verts_tgt"].packed] + extra, out["cano_handle_vert_idx"], faces.packed)
                 export_meshes(mesh_dir, infos, ext, dict(zip(("source", "canonical", "deformed", "target"), sets)), handle, f,
-                              pred.counts, faces.counts, dict(zip(("source", "deformed", "target"), sets[4:])))
+                              pred.counts, faces.counts, dict(zip(("source", "deformed", "target"), sets[4:7] if with_normals else [])),
+                              sets[-1].view(np.int32).astype(np.uint8) if with_colors else None)
         means, left_out = filtered_means(rows, metrics)
         say("mean over {} pairs (values <= 1.0 only)  ".format(len(rows)) + "  ".join("{} {:.6e}".format(k, means[k]) for k in metrics)
             + "  left out: " + ", ".join("{} {}".format(k, left_out[k]) for k in metrics))
